@@ -7,12 +7,12 @@ A "step" is one pass of the hot path over one batch of `--batch` device-resident
 launch through the C ABI).  Images of a batch are distinct buffers (default 4 x 256 MiB = 1 GiB per GPU,
 four times the 256 MiB Infinity Cache), so every step streams its source from HBM.
 
-Timing: W warm-up steps, then the block of K steps is run `repeats` times back to back between two fences
-(barrier + device synchronize); `repeats` is chosen from the warm-up so that the timed GPU leg lasts about
-`--min-seconds` (6 s by default: a 5-second telemetry sampler then sees the GPU busy); ms_per_step = elapsed /
-(repeats * K), taken as the MAX over ranks.  Nothing but the launches runs inside that wall-clock window: ONE pair of
-HIP events on the launch stream brackets the whole timed region, and its elapsed time / launches is the average launch
-duration behind `roofline` (rocprofv3 --kernel-trace of the same command agrees: profiles/).  Per-step min / median /
+Timing: W warm-up steps, then exactly K = `--steps` steps back to back between two fences (barrier + device
+synchronize); ms_per_step = elapsed / K, taken as the MAX over ranks.  On request the block of K steps is repeated:
+`--repeats R` times, or as often as it takes to last about `--min-seconds` (e.g. 6 s, so that a 5-second telemetry
+sampler sees the GPU busy); ms_per_step is then elapsed / (repeats * K).  Nothing but the launches runs inside that
+wall-clock window: ONE pair of HIP events on the launch stream brackets the whole timed region, and its elapsed time /
+launches is the average launch duration behind `roofline` (rocprofv3 --kernel-trace of the same command agrees: profiles/).  Per-step min / median /
 max (`timed.step_ms`) come from a separate pass of at most 512 steps with an event pair each.
 
 Default invocation (one GPU, config 2): `roofline.traffic` is measured by this run -- two short child passes under
@@ -27,6 +27,11 @@ Weak scaling over the batch (`--shard batch`, default): every rank resamples its
 data-path collective -- the request block is broadcast once over RCCL before timing; `--gather` adds an RCCL
 gather of the outputs to rank 0, reported separately.  `--shard rows`: ONE image per step split into dst row
 bands over the ranks (strong scaling; each rank generates only the source rows its band reads).
+
+`--dump-outputs DIR`: after the timed steps, the outputs of the last one (the dst images a caller receives) are written
+as float32 .npy files under DIR -- `dst.npy` whole, or, past 64 MB, `dst_rows.npy` with a fixed seeded sample of its
+rows and `dst_row_index.npy` with their flat row numbers (float64); `_rank<r>` is appended to the names with several
+ranks.  Inputs are the seeded synthetic images, so two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -504,6 +509,30 @@ def cfg4_sharded(aai, torch, dist, D, world, rank, cdev, policy, fence, mock):
             "note": "kernel-only, every rank's images device-resident, no collective on the data path"}
 
 
+# ---- --dump-outputs ------------------------------------------------------------------------------------------------------
+DUMP_BYTES = 64 * 1000 * 1000         # all .npy files of one run together
+
+
+def dump_outputs(torch, dst, n_rows, width, out_dir, name, budget):
+    """Write the device tensor dst (n_rows rows of `width` float32 pixels; nothing when n_rows is 0) as out_dir/<name>.npy,
+    or, when that exceeds `budget` bytes, a sample of its rows: chosen by a fixed seed, in ascending order, as
+    <name>_rows.npy (float32, rows x width) and their flat row numbers as <name>_row_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if n_rows == 0:
+        return
+    assert dst.numel() == n_rows * width, (tuple(dst.shape), n_rows, width)
+    header = 4096                      # room for the .npy headers
+    if n_rows * width * 4 + header <= budget:
+        np.save(os.path.join(out_dir, name + ".npy"), dst.float().cpu().numpy())
+        return
+    k = max(1, min(n_rows, (budget - 2 * header) // (width * 4 + 8)))
+    idx = np.sort(np.random.default_rng(20240611).choice(n_rows, size=k, replace=False))
+    rows = dst.reshape(-1, width)[torch.from_numpy(idx).to(dst.device)]
+    np.save(os.path.join(out_dir, name + "_rows.npy"), rows.float().cpu().numpy())
+    np.save(os.path.join(out_dir, name + "_row_index.npy"), idx.astype(np.float64))
+
+
 # ---- one rank -----------------------------------------------------------------------------------------------------
 def worker(args):
     import ctypes
@@ -648,12 +677,15 @@ def worker(args):
             step()
         fence()
         return
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
-    probe = max(time.perf_counter() - t0, 1e-6)
-    repeats = args.repeats if args.repeats > 0 else max(1, min(1000000, int(args.min_seconds / probe + 0.999)))
+    # --steps is the number of timed steps unless repeats of that block are asked for (--repeats, or --min-seconds: sized by a probe)
+    repeats = args.repeats if args.repeats > 0 else 1
+    if args.repeats <= 0 and args.min_seconds > 0:
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        probe = max(time.perf_counter() - t0, 1e-6)
+        repeats = max(1, min(1000000, int(args.min_seconds / probe + 0.999)))
     if dist.is_initialized():
         t = torch.tensor([repeats], dtype=torch.int64, device=cdev)
         dist.broadcast(t, src=0)
@@ -675,6 +707,9 @@ def worker(args):
     fence()
     elapsed = time.perf_counter() - t0
     kernel_ms = e0.elapsed_time(e1) / n_timed if e0 else elapsed / n_timed * 1e3        # average launch duration on the stream
+    if args.dump_outputs and not mock:
+        # what the last timed step computed: batch mode holds B whole images, rows mode this rank's band
+        dump_outputs(torch, dst, B * out_rows, dW, args.dump_outputs, "dst" if world == 1 else "dst_rank%d" % rank, DUMP_BYTES // world)
     # per-step spread, outside the timed region: at most 512 steps with an event pair each
     n_stat = min(n_timed, 512)
     if mock:
@@ -813,16 +848,18 @@ def main():
                     help="source element type (the headline metric is f32; u8/u16 exercise the typed entry points)")
     ap.add_argument("--shard", default="batch", choices=["batch", "rows"],
                     help="batch: every rank resamples its own images (weak scaling); rows: ONE image split into dst row bands (strong scaling)")
-    ap.add_argument("--min-seconds", type=float, default=6.0, help="the timed leg repeats the block of --steps until it lasts about this long "
-                    "(default 6 s: longer than a 5-second telemetry sampling period)")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the timed block of --steps until it lasts about this long "
+                    "(e.g. 6 s: longer than a 5-second telemetry sampling period; default 0 = time exactly --steps steps)")
     ap.add_argument("--configs", default="auto", choices=["auto", "on", "off"],
                     help="append the per-configuration block (every BASELINE config, kernel-only, with CPU baselines): auto = the default one-GPU config-2 run")
     ap.add_argument("--traffic", default="auto", choices=["auto", "off"],
                     help="measure roofline.traffic in this run (two rocprofv3 --pmc child passes before the GPU is touched): auto = one GPU, no launcher")
     ap.add_argument("--deadline", type=float, default=1500.0, help="--gpus N self-launch: kill the ranks and fail after this many seconds")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)     # a counter pass of measure_traffic()
-    ap.add_argument("--repeats", type=int, default=0, help="fix the number of repeats of the --steps block (0 = from --min-seconds)")
+    ap.add_argument("--repeats", type=int, default=0, help="repeat the timed block of --steps this many times (0 = once, or from --min-seconds)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32; a fixed seeded sample of rows past 64 MB)")
     ap.add_argument("--cpu-scale", type=float, default=1.0, help="scale the CPU baseline's time budgets (15 s headline, 6 s per configuration); tests use a small one")
     ap.add_argument("--cpu-procs", type=int, default=-1, help="processes of the extra multi-process CPU baseline (default: min(16, cores) for cfg4, else none)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],

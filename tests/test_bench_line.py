@@ -34,3 +34,27 @@ def test_default_bench_line_fits_the_drivers_tail_and_names_every_baseline_confi
     by = {c["name"]: c for c in d["configs"]}
     assert "aai_cell_kernel" in by["cfg3"]["kernel"] and "aai_cell_kernel" in by["cfg5"]["kernel"]
     assert by["cfg4"]["images"] == 64 and by["cfg2"]["dst"] == [2048, 2048] and by["cfg5"]["dst"] == [23170, 23170]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the batch the timed path computed, as float32 DIR/dst.npy, here config 1 (2 images of 512 x 512 ->
+    256 x 256); image b is the seeded synthetic image b + 1, so the dump must match the CPU oracle on it."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from oracle import pyoracle as po
+    if not po.have_oracle():
+        po.build()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg1", "--batch", "2", "--steps", "3", "--warmup", "1",
+                        "--traffic", "off", "--configs", "off", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads(p.stdout)
+    assert d["timed"]["steps_timed"] == 3 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["dst.npy"]
+    dst = np.load(os.path.join(tmp_path, "dst.npy"))
+    assert dst.dtype == np.float32 and dst.shape == (2, 256, 256)
+    for b in range(2):
+        gold = po.oracle_run(po.MODE_EXACT, po.synth_image(512, 512, b + 1).astype(np.float64), 2.0, 1.0, (255.5, 255.5), 0.0).dst
+        err = np.abs(dst[b] - gold) / np.maximum(np.abs(gold), 1e-3)
+        assert err.max() <= 1e-5, (b, float(err.max()))

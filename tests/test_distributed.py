@@ -117,6 +117,19 @@ def _run_bench(*extra, timeout=240):
     return p.returncode, [json.loads(l) for l in lines], p.stdout, p.stderr
 
 
+def test_bench_times_exactly_the_steps_asked_for():
+    """Without --min-seconds / --repeats the timed region is --steps steps, and ms_per_step is its wall clock divided by them."""
+    import json
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mock-device", "--no-cpu-baseline", "--steps", "7", "--warmup", "2"],
+                       capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout)
+    assert d["steps"] == 7 and d["timed"]["repeats"] == 1 and d["timed"]["steps_timed"] == 7
+    assert abs(d["ms_per_step"] * 7e-3 - d["timed"]["seconds"]) < 1e-6 and d["ms_per_step"] > 0
+
+
 def test_bench_self_launches_two_ranks_and_relays_one_line():
     """`python bench.py --gpus 2` without torch.distributed.run: the parent starts the ranks itself (fresh processes with
     RANK / WORLD_SIZE / MASTER_* set), rank 0's single JSON line comes back through it and carries what the world looked

@@ -12,14 +12,20 @@ synchronize); ms_per_step = elapsed / K, taken as the MAX over ranks.  On reques
 `--repeats R` times, or as often as it takes to last about `--min-seconds` (e.g. 6 s, so that a 5-second telemetry
 sampler sees the GPU busy); ms_per_step is then elapsed / (repeats * K).  Nothing but the launches runs inside that
 wall-clock window: ONE pair of HIP events on the launch stream brackets the whole timed region, and its elapsed time /
-launches is the average launch duration behind `roofline` (rocprofv3 --kernel-trace of the same command agrees: profiles/).  Per-step min / median /
-max (`timed.step_ms`) come from a separate pass of at most 512 steps with an event pair each.
+launches is the average launch duration behind `roofline` (rocprofv3 --kernel-trace of the same command agrees: profiles/).
 
-Default invocation (one GPU, config 2): `roofline.traffic` is measured by this run -- two short child passes under
-rocprofv3 (--pmc FETCH_SIZE, --pmc WRITE_SIZE; MI355X_MICROARCH.md HBM section, FETCH_SIZE x2 on gfx950) started before
-this process touches the GPU; where rocprofv3 is missing the figure committed under profiles/ is quoted and says so --
-and a `configs` block follows the headline: every BASELINE.json configuration (plus the reference's own default call),
-kernel-only, with the plan's launch shape, its cold `prepare_ms` and the unmodified reference timed on this host's cores.
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes its outputs on request
+(`--dump-outputs`) and prints the line.  Everything else it can measure runs with `--full` only:
+  * per-step min / median / max (`timed.step_ms`) from a separate pass of at most 512 steps with an event pair each;
+  * `roofline.traffic` measured by this run (one GPU, no launcher) -- two short child passes of its workload under rocprofv3
+    (--pmc FETCH_SIZE, --pmc WRITE_SIZE; MI355X_MICROARCH.md HBM section, FETCH_SIZE x2 on gfx950) started before this
+    process touches the GPU; without them, or where rocprofv3 is missing, the figure committed under profiles/ is quoted
+    and says so;
+  * `cpu_baseline`: the unmodified reference timed on this host's cores (`--no-cpu-baseline` leaves it out);
+  * one GPU, config 2: a `configs` block after the headline -- every BASELINE.json configuration (plus the reference's own
+    default call), kernel-only, with the plan's launch shape, its cold `prepare_ms` and the reference's CPU figures;
+  * several ranks, config 2: a `cfg4` entry, BASELINE config 4's 64 images sharded over the ranks.
+`--configs off` / `--traffic off` drop a part of `--full`.
 
 Multi-GPU: `python bench.py --gpus N` starts N worker processes itself (one per GPU; the parent makes no GPU call
 and relays rank 0's single JSON line), or run it under `python -m torch.distributed.run --nproc-per-node N`.
@@ -548,18 +554,20 @@ def worker(args):
     mock = args.mock_device          # CPU rehearsal of the launch / collective / reporting path (tests): no GPU call at all
     if args.mock_fail_rank == rank:
         sys.exit(3)
+    full = args.full                 # everything besides the headline figure (module docstring)
     # the worker processes of the multi-process CPU baseline (config 4) are started BEFORE this process touches the GPU
-    want_configs = args.configs == "on" or (args.configs == "auto" and world == 1 and args.workload == "cfg2" and not args.custom and
-                                            not mock and not args.traffic_child and args.shard == "batch" and args.src_dtype == "f32")
+    want_configs = full and (args.configs == "on" or (args.configs == "auto" and world == 1 and args.workload == "cfg2" and not args.custom and
+                                                      not mock and not args.traffic_child and args.shard == "batch" and args.src_dtype == "f32"))
     cpu_procs = args.cpu_procs if args.cpu_procs >= 0 else (min(16, os.cpu_count() or 1) if (args.workload == "cfg4" or want_configs) else 0)
     cpu_pool = None
     cpu_note = None
-    if under_profiler() and not args.no_cpu_baseline and not mock:
+    if full and under_profiler() and not args.no_cpu_baseline and not mock:
         # A profiler's preload has initialised the GPU in THIS process: starting worker interpreters from it (each inheriting the
         # preload) is the hop spawn_ranks() and measure_traffic() refuse too.  The CPU legs are skipped and the line says so.
         args.no_cpu_baseline = True
         cpu_note = "skipped: running under a profiler preload (no child processes from a GPU-initialised process)"
-    if cpu_procs > 1 and world == 1 and not args.no_cpu_baseline and not mock:
+    want_cpu = full and not args.no_cpu_baseline and not mock
+    if cpu_procs > 1 and world == 1 and want_cpu:
         from multiprocessing import get_context
         cpu_pool = get_context("spawn").Pool(cpu_procs)
     if args.gpus > 1 or world > 1 or args.force_dist:
@@ -710,11 +718,12 @@ def worker(args):
     if args.dump_outputs and not mock:
         # what the last timed step computed: batch mode holds B whole images, rows mode this rank's band
         dump_outputs(torch, dst, B * out_rows, dW, args.dump_outputs, "dst" if world == 1 else "dst_rank%d" % rank, DUMP_BYTES // world)
-    # per-step spread, outside the timed region: at most 512 steps with an event pair each
+    # --full: per-step spread, outside the timed region: at most 512 steps with an event pair each
     n_stat = min(n_timed, 512)
-    if mock:
+    per_step = None
+    if full and mock:
         per_step = [elapsed / n_timed * 1e3] * n_stat
-    else:
+    elif full:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_stat)]
         for a, b in evs:
             a.record()
@@ -752,9 +761,9 @@ def worker(args):
         fence()
         gather_ms = (time.perf_counter() - g0) * 1e3
 
-    # BASELINE config 4 (64 images over the ranks) rides along on every multi-rank batch run of the headline
+    # --full: BASELINE config 4 (64 images over the ranks) rides along on every multi-rank batch run of the headline
     cfg4_rank = None
-    if world > 1 and dist.is_initialized() and args.configs != "off" and not rows_mode and args.workload == "cfg2" and 64 % world == 0:
+    if full and world > 1 and dist.is_initialized() and args.configs != "off" and not rows_mode and args.workload == "cfg2" and 64 % world == 0:
         if not mock:
             del src, dst
             torch.cuda.empty_cache()
@@ -775,7 +784,6 @@ def worker(args):
                                      "NOT collected by this run (%s; this run: %s)" % (pmc.get("measured", "see profiles/README.md"), args.traffic_note or "not attempted")
             except Exception:
                 pass
-        mid = len(per_step) // 2
         line = {
             "metric": "Mpixels/s (output) and achieved HBM GB/s, 8192^2->2048^2 fp32, 1/2/4/8 GPU",
             "value": out_pix / elapsed / 1e6,
@@ -788,9 +796,7 @@ def worker(args):
                        if mode == MODE_AREA else "%s: %s" % (args.workload, desc),
                        "images_per_gpu_per_step": B if not rows_mode else 1.0 / world, "src_bytes_per_gpu": esz * W * src_rows * B,
                        "parallelism": ("one image in %d row bands" if rows_mode else "batch-sharded x%d") % world},
-            "timed": {"repeats": repeats, "steps_timed": n_timed, "seconds": elapsed,
-                      "step_ms": {"min": per_step[0], "median": per_step[mid], "max": per_step[-1], "steps": len(per_step),
-                                  "note": "separate pass with one HIP event pair per step; the timed region itself holds launches only"}},
+            "timed": {"repeats": repeats, "steps_timed": n_timed, "seconds": elapsed},
             "plan": {"shape": plan_shape, "first_call_ms": first_call_ms,
                      "note": "first_call_ms = plan creation (tables, one-off scans, K1 launch-shape measurement) + one launch, wall clock"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -800,13 +806,16 @@ def worker(args):
             "distributed": {"backend": backend, "world_size_seen": world_seen, "kernel_ms_per_rank": rank_ms,
                             "value_compute_only": out_pix / elapsed / 1e6},
         }
+        if per_step:
+            line["timed"]["step_ms"] = {"min": per_step[0], "median": per_step[len(per_step) // 2], "max": per_step[-1], "steps": len(per_step),
+                                        "note": "separate pass with one HIP event pair per step; the timed region itself holds launches only"}
         line["host"] = {"cpu_model": _cpu_model(), "host_cpus": os.cpu_count()}
         if mock:
             line["mock"] = True
         if gather_ms is not None:
             line["distributed"]["gather_ms"] = gather_ms
             line["distributed"]["value_with_gather"] = total_images * dW * dH / (elapsed / n_timed + gather_ms * 1e-3) / 1e6
-        if world == 1 and not args.no_cpu_baseline and not mock and mode in (MODE_AREA, MODE_FAST):
+        if world == 1 and want_cpu and mode in (MODE_AREA, MODE_FAST):
             line["cpu_baseline"] = cpu_baseline(args.workload, budget_s=15.0 * args.cpu_scale, procs=cpu_procs if args.workload == "cfg4" else 0, pool=cpu_pool)
             line["cpu_baseline"]["gpu_over_cpu"] = line["value"] / line["cpu_baseline"]["value"]
         if cpu_note:
@@ -814,7 +823,7 @@ def worker(args):
         if want_configs:
             del src, dst
             torch.cuda.empty_cache()
-            line["configs"] = config_block(aai, torch, policy, line.get("cpu_baseline"), cpu_procs, cpu_pool, not args.no_cpu_baseline, args.cpu_scale)
+            line["configs"] = config_block(aai, torch, policy, line.get("cpu_baseline"), cpu_procs, cpu_pool, want_cpu, args.cpu_scale)
             line["configs_note"] = ("per BASELINE configuration, kernel-only: ms per launch, output Mpixels/s, algorithmic GB/s and fraction of the 8 TB/s HBM peak, "
                                     "cold aai_prepare ms, graph_ms = the same launches replayed from a HIP graph (launch-bound configurations only), x8_ms = 8 distinct images in one launch; cpu = [Mpixels/s of the unmodified reference on 1 core of this host, output pixels of its sample, seconds]")
         if cfg4_rank is not None:
@@ -850,14 +859,18 @@ def main():
                     help="batch: every rank resamples its own images (weak scaling); rows: ONE image split into dst row bands (strong scaling)")
     ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the timed block of --steps until it lasts about this long "
                     "(e.g. 6 s: longer than a 5-second telemetry sampling period; default 0 = time exactly --steps steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline too: per-step spread, roofline.traffic, CPU baselines, the configs block "
+                         "(one GPU) or the cfg4 entry (several ranks); a plain run only sets up, warms up, times --steps steps and reports")
     ap.add_argument("--configs", default="auto", choices=["auto", "on", "off"],
-                    help="append the per-configuration block (every BASELINE config, kernel-only, with CPU baselines): auto = the default one-GPU config-2 run")
+                    help="with --full: the per-configuration block (every BASELINE config, kernel-only, with CPU baselines) and, with several ranks, "
+                         "the cfg4 entry; auto = the one-GPU config-2 run")
     ap.add_argument("--traffic", default="auto", choices=["auto", "off"],
-                    help="measure roofline.traffic in this run (two rocprofv3 --pmc child passes before the GPU is touched): auto = one GPU, no launcher")
+                    help="with --full: measure roofline.traffic in this run (two rocprofv3 --pmc child passes before the GPU is touched): auto = one GPU, no launcher")
     ap.add_argument("--deadline", type=float, default=1500.0, help="--gpus N self-launch: kill the ranks and fail after this many seconds")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)     # a counter pass of measure_traffic()
     ap.add_argument("--repeats", type=int, default=0, help="repeat the timed block of --steps this many times (0 = once, or from --min-seconds)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32; a fixed seeded sample of rows past 64 MB)")
     ap.add_argument("--cpu-scale", type=float, default=1.0, help="scale the CPU baseline's time budgets (15 s headline, 6 s per configuration); tests use a small one")
@@ -870,12 +883,14 @@ def main():
     ap.add_argument("--mock-device", action="store_true", help=argparse.SUPPRESS)      # tests: launch / collective / report path on CPU
     ap.add_argument("--mock-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.configs == "on" and not args.full:
+        ap.error("--configs on is a part of --full")
 
     # No launcher around us and more than one GPU asked for: become the launcher (and never touch the GPU ourselves).
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus, sys.argv[1:], args.deadline)
-    args.traffic_bytes, args.traffic_note = None, None
-    if (args.traffic == "auto" and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.mock_device and not args.traffic_child and
+    args.traffic_bytes, args.traffic_note = None, (None if args.full else "not attempted without --full")
+    if (args.full and args.traffic == "auto" and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.mock_device and not args.traffic_child and
             not args.force_dist and args.shard == "batch" and os.environ.get("AAI_BENCH_TRAFFIC", "1") != "0"):
         child = ["--traffic-child", "--traffic", "off", "--configs", "off", "--no-cpu-baseline", "--workload", args.workload, "--batch", str(args.batch),
                  "--steps", "8", "--warmup", "2", "--policy", args.policy, "--src-dtype", args.src_dtype] + (["--custom", args.custom] if args.custom else [])

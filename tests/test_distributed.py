@@ -135,7 +135,7 @@ def test_bench_self_launches_two_ranks_and_relays_one_line():
     RANK / WORLD_SIZE / MASTER_* set), rank 0's single JSON line comes back through it and carries what the world looked
     like from inside the collective backend.  The device step is mocked: this rehearses spawn, rendezvous (gloo),
     request broadcast, barrier-fenced timing, max-over-ranks and per-rank reporting on the CPU."""
-    rc, lines, out, err = _run_bench("--gpus", "2", "--backend", "gloo")
+    rc, lines, out, err = _run_bench("--gpus", "2", "--backend", "gloo", "--full")
     assert rc == 0, err[-2000:]
     assert len(lines) == 1 and out.strip().count("\n") == 0, out          # ONE line on stdout, nothing else
     d = lines[0]
@@ -145,7 +145,7 @@ def test_bench_self_launches_two_ranks_and_relays_one_line():
     assert d["timed"]["steps_timed"] == d["timed"]["repeats"] * d["steps"] and d["timed"]["repeats"] >= 1
     assert d["timed"]["step_ms"]["min"] <= d["timed"]["step_ms"]["median"] <= d["timed"]["step_ms"]["max"]
     assert abs(d["ms_per_step"] * d["timed"]["steps_timed"] * 1e-3 - d["timed"]["seconds"]) < 1e-6
-    # BASELINE config 4 (64 images over the ranks) rides along on a multi-rank headline run: 32 images per rank here
+    # BASELINE config 4 (64 images over the ranks) rides along on a multi-rank --full headline run: 32 images per rank here
     assert len(d["cfg4"]["ms_per_rank"]) == 2 and "32 images per rank" in d["cfg4"]["workload"] and d["cfg4"]["mpix_s"] > 0
     assert len(out.strip()) < 8000                                         # the driver keeps an 8 KB tail of stdout
     # row bands of one image: same launch path, strong scaling, half an image per rank
@@ -155,6 +155,20 @@ def test_bench_self_launches_two_ranks_and_relays_one_line():
     # one rank keeps the old shape (no process group, no spawn)
     rc, lines, out, err = _run_bench()
     assert rc == 0 and len(lines) == 1 and lines[0]["n_gpus"] == 1 and lines[0]["distributed"]["backend"] is None
+
+
+def test_plain_bench_run_times_and_reports_only():
+    """Without --full a run measures nothing besides its headline: no per-step pass, no cfg4 entry with several ranks, no CPU
+    baseline; the headline fields are all there.  --configs on belongs to --full and is refused without it."""
+    for extra in ((), ("--gpus", "2", "--backend", "gloo")):
+        rc, lines, out, err = _run_bench(*extra)
+        assert rc == 0 and len(lines) == 1, (extra, err[-2000:])
+        d = lines[0]
+        assert all(k in d for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")), sorted(d)
+        assert d["timed"]["steps_timed"] == d["timed"]["repeats"] * d["steps"] and d["value"] > 0
+        assert "step_ms" not in d["timed"] and not {"cfg4", "cpu_baseline", "configs"} & set(d), (extra, sorted(d))
+    rc, lines, out, err = _run_bench("--configs", "on")
+    assert rc != 0 and not lines and "--full" in err
 
 
 def test_bench_parent_fails_when_a_rank_fails():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""DESIGN.md section 7's table from a default bench.py line: python tools/design_table.py profiles/rNN_bench_default.json"""
+"""DESIGN.md section 7's table from a `bench.py --full` line: python tools/design_table.py profiles/rNN_bench_default.json"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 c = {e["name"]: e for e in d["configs"]}

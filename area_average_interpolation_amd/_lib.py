@@ -8,8 +8,7 @@ import os
 import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (tools/ may point AAI_LIB at the experiments build, `make -C csrc exp` -> libaai_hip_exp.so, whose launch heuristics read the
-# AAI_* environment switches; the product library ignores them)
+# (AAI_LIB points the loader at another build of the library, e.g. `make -C csrc OUT=... OBJ=...`, to compare two builds)
 LIB_PATH = os.environ.get("AAI_LIB") or os.path.join(_HERE, "libaai_hip.so")
 
 # status codes (include/aai.h)

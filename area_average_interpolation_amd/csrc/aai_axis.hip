@@ -22,7 +22,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 
 namespace aai {
 
@@ -202,8 +201,7 @@ __device__ __forceinline__ float horizontal_pass(const float *line, int off, int
 }
 
 // NT: nontemporal source loads.
-// A workgroup owns `rowsPerBlock` consecutive output rows of its 4 strips (or, with `interleave`, the rows
-// blockIdx.y, blockIdx.y + gridDim.y, ...).  Measured on MI355X (tools/tune_axis.py, profiles/): ONE output
+// A workgroup owns `rowsPerBlock` consecutive output rows of its 4 strips.  Measured on MI355X (profiles/r01_axis_tune_*.txt): ONE output
 // row per workgroup is fastest by a wide margin (8192^2 -> 2048^2: 6.8 TB/s at 1 row, 6.3 at 2, 5.3 at 8,
 // 4.8 at 32): workgroups are dispatched in grid order, so small workgroups make the whole chip sweep the
 // image top to bottom together and the HBM pages of a source row are read by all CUs at about the same
@@ -215,18 +213,13 @@ template <bool NT, typename T, bool CH>
 __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, const AxisEntry *__restrict__ laneTab,
                                                                 const AxisEntry *__restrict__ rowTab, const AxisStrip *__restrict__ strips,
                                                                 const T *__restrict__ src, ImageView sv,
-                                                                float *__restrict__ dst, ImageView dv,
-                                                                int rowsPerBlock, int interleave, int swapXY)
+                                                                float *__restrict__ dst, ImageView dv, int rowsPerBlock)
 {
     __shared__ __attribute__((aligned(16))) float lds[kWaves][64 * VEC + 8];   // +8 keeps the lines 16-byte aligned and apart
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: strip/row tables load through the scalar cache
-    // swapXY: the grid is launched (rows, strip blocks) so that consecutive workgroups -- which go to consecutive XCDs --
-    // take consecutive output ROWS of one strip block instead of the strip blocks of one row
-    const int bX = swapXY ? (int)blockIdx.y : (int)blockIdx.x, bY = swapXY ? (int)blockIdx.x : (int)blockIdx.y;
-    const int gY = swapXY ? (int)gridDim.x : (int)gridDim.y;
-    const int strip = bX * kWaves + wave;
+    const int strip = (int)blockIdx.x * kWaves + wave;
     if (strip >= a.nStrips) return;   // waves are independent: no barrier is skipped by leaving early
 
     typedef int i4s __attribute__((ext_vector_type(4)));
@@ -239,9 +232,8 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
     const int colc = min(col, a.srcW - VEC);        // srcW >= VEC here (narrower images use the wide kernel)
     const int shift = col - colc;                    // 0 away from the right edge
 
-    const int rowStart = interleave ? bY : bY * rowsPerBlock;
-    const int rowStep = interleave ? gY : 1;
-    const int rowEnd = interleave ? a.nB : min(rowStart + rowsPerBlock, a.nB);
+    const int rowStart = (int)blockIdx.y * rowsPerBlock;
+    const int rowEnd = min(rowStart + rowsPerBlock, a.nB);
     const int nOut = st.k1 - st.k0;
     // interleaved channels: taps `step` elements apart, dst element of lane entry ka split into (pixel, channel)
     const int step = CH ? a.tapStep : 1;
@@ -250,7 +242,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
         return CH ? (int64_t)(ka / a.outChan) * a.outStrideA + ka % a.outChan : (int64_t)ka * a.outStrideA;
     };
 
-    if (!CH && nOut <= 64 && (a.outStrideB == 1 || a.outStrideB == -1) && rowStep == 1) {
+    if (!CH && nOut <= 64 && (a.outStrideB == 1 || a.outStrideB == -1)) {
         // Quadrants 1 and 3 (pre-rotation by 90 / 270 degrees): the lane axis runs along dst y, so the output
         // rows of this workgroup are CONSECUTIVE DST COLUMNS of each lane's dst row.  Keep eight of them in
         // registers and write them as two 16-byte stores per lane instead of eight 4-byte stores a row pitch
@@ -303,7 +295,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
                     if (kb0 + j < rowEnd) orow[(int64_t)(kb0 + j) * a.outStrideB] = acc[j];
             }
         }
-    } else if (!CH && nOut <= 256 && (a.outStrideB == 1 || a.outStrideB == -1) && rowStep == 1) {
+    } else if (!CH && nOut <= 256 && (a.outStrideB == 1 || a.outStrideB == -1)) {
         // Quadrants 1 and 3 at ratios below 4 (65..256 outputs per strip): up to four outputs per lane, interleaved
         // across the wave (k = k0 + lane + 64 q, so that neighbouring lanes read neighbouring windows of the LDS line),
         // each holding FOUR consecutive dst columns in registers = one 16-byte store per output and chunk instead of
@@ -357,7 +349,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
         const Win c = load_win(laneTab, live ? st.k0 + lane : st.k0);
         const int off = c.s0 - st.x0, span = taps(c);
         const int64_t outCol = out_off(st.k0 + lane);
-        for (int kb = rowStart; kb < rowEnd; kb += rowStep) {
+        for (int kb = rowStart; kb < rowEnd; ++kb) {
             const Win e = load_win(rowTab, kb);
             const Cols v = vertical_pass<NT, T>(img, sv.rowStride, colc, e);
             __builtin_amdgcn_wave_barrier();
@@ -372,7 +364,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
         const int nq = min(max(st.k1 - kq, 0), 4);                   // how many of this lane's four outputs exist
         const Win c0 = load_win(laneTab, nq > 0 ? kq : st.k0), c1 = load_win(laneTab, nq > 1 ? kq + 1 : st.k0);
         const Win c2 = load_win(laneTab, nq > 2 ? kq + 2 : st.k0), c3 = load_win(laneTab, nq > 3 ? kq + 3 : st.k0);
-        for (int kb = rowStart; kb < rowEnd; kb += rowStep) {
+        for (int kb = rowStart; kb < rowEnd; ++kb) {
             const Win e = load_win(rowTab, kb);
             const Cols v = vertical_pass<NT, T>(img, sv.rowStride, colc, e);
             __builtin_amdgcn_wave_barrier();
@@ -393,7 +385,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
         }
     } else {
         // Many outputs per strip (up-sampling, transposed quadrants at small ratios): lanes walk the outputs.
-        for (int kb = rowStart; kb < rowEnd; kb += rowStep) {
+        for (int kb = rowStart; kb < rowEnd; ++kb) {
             const Win e = load_win(rowTab, kb);
             const Cols v = vertical_pass<NT, T>(img, sv.rowStride, colc, e);
             __builtin_amdgcn_wave_barrier();
@@ -460,23 +452,23 @@ __device__ __forceinline__ void tile_columns(const T *__restrict__ img, int64_t 
     }
 }
 
-// COOP: the four waves of a workgroup take ONE strip and four consecutive groups of 16 output rows, meet at a barrier and store
+// The four waves of a workgroup take ONE strip and four consecutive groups of 16 output rows, meet at a barrier and store
 // together -- lane = one of 64 consecutive dst x, read from the four waves' tiles: 256 contiguous bytes per dst row and store
 // instruction instead of four 64-byte segments.
 constexpr int kTileWaveFloatsCoop = (kTileWaveFloats + 31) / 32 * 32 + 16;      // tiles 16 banks apart: the joint reads are conflict free
-template <bool NT, typename T, bool COOP>
+template <bool NT, typename T>
 __global__ __launch_bounds__(kWaves * 64) void aai_axis_tile_kernel(AxisLaunch a, const AxisEntry *__restrict__ laneTab,
                                                                      const AxisEntry *__restrict__ rowTab, const AxisStrip *__restrict__ strips,
                                                                      const T *__restrict__ src, ImageView sv,
                                                                      float *__restrict__ dst, ImageView dv)
 {
-    constexpr int kWaveFloats = COOP ? kTileWaveFloatsCoop : kTileWaveFloats;
+    constexpr int kWaveFloats = kTileWaveFloatsCoop;
     __shared__ __attribute__((aligned(16))) float smem[kWaves * kWaveFloats];     // 72 KiB: two workgroups per CU
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int strip = COOP ? (int)blockIdx.x : (int)blockIdx.x * kWaves + wave;
-    if (strip >= a.nStrips) return;   // (not COOP: waves are independent, no s_barrier anywhere; COOP: the whole workgroup leaves)
+    const int strip = (int)blockIdx.x;
+    if (strip >= a.nStrips) return;   // (the whole workgroup leaves)
 
     typedef int i4s __attribute__((ext_vector_type(4)));
     const i4s stq = reinterpret_cast<const i4s *>(strips)[strip];
@@ -490,7 +482,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_tile_kernel(AxisLaunch a
     const int shift = col - colc;
     const int nOut = st.k1 - st.k0;                              // <= 256
     const int nq = (nOut + 63) >> 6;                             // wave-uniform
-    const int kb0 = COOP ? ((int)blockIdx.y * kWaves + wave) * kTileCols : (int)blockIdx.y * kTileCols;
+    const int kb0 = ((int)blockIdx.y * kWaves + wave) * kTileCols;
     const int nCols = max(0, min(kTileCols, a.nB - kb0));
 
     const int kl = st.k0 + lane;
@@ -513,23 +505,14 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_tile_kernel(AxisLaunch a
     // strip still holds more than 64 outputs): four; anything taller takes the plain path
     if (a.maxRowSpan <= 4) tile_columns<NT, T, 4, 8>(img, sv.rowStride, colc, rowTab, kb0, nCols, finish_column);
     else tile_columns<NT, T, 8, 4>(img, sv.rowStride, colc, rowTab, kb0, nCols, finish_column);
-    if (COOP) {
-        __syncthreads();
-        // lane = dst x within the workgroup's 64 output rows (kb), read from the tile of the wave that computed it; wave w stores
-        // the dst rows r = w, w + 4, ...
-        const int kbBase = (int)blockIdx.y * kWaves * kTileCols;
-        const float *from = smem + (lane >> 4) * kWaveFloats + 64 * VEC + 8 + (lane & (kTileCols - 1));
-        if (kbBase + lane < a.nB)
-            for (int r = wave; r < nOut; r += kWaves)
-                out[(int64_t)(st.k0 + r) * a.outStrideA + (int64_t)(kbBase + lane) * a.outStrideB] = from[r * kTilePitch];
-        return;
-    }
-    __builtin_amdgcn_wave_barrier();
-    // store: four dst rows x 16 dst columns per instruction
-    const int jr = lane & (kTileCols - 1), rr = lane >> 4;
-    if (jr < nCols)
-        for (int r = rr; r < nOut; r += 64 / kTileCols)
-            out[(int64_t)(st.k0 + r) * a.outStrideA + (int64_t)(kb0 + jr) * a.outStrideB] = tile[r * kTilePitch + jr];
+    __syncthreads();
+    // lane = dst x within the workgroup's 64 output rows (kb), read from the tile of the wave that computed it; wave w stores
+    // the dst rows r = w, w + 4, ...
+    const int kbBase = (int)blockIdx.y * kWaves * kTileCols;
+    const float *from = smem + (lane >> 4) * kWaveFloats + 64 * VEC + 8 + (lane & (kTileCols - 1));
+    if (kbBase + lane < a.nB)
+        for (int r = wave; r < nOut; r += kWaves)
+            out[(int64_t)(st.k0 + r) * a.outStrideA + (int64_t)(kbBase + lane) * a.outStrideB] = from[r * kTilePitch];
 }
 
 // Fallback for footprints wider than one strip (down-sampling by more than ~250:1): one thread per output
@@ -558,27 +541,6 @@ __global__ __launch_bounds__(256) void aai_axis_wide_kernel(AxisLaunch a, const 
 
 }  // namespace
 
-// Launch-shape overrides for experiments (tools/tune_axis.py), in the experiments build only (make exp, -DAAI_EXPERIMENTS):
-// AAI_AXIS_TUNE="nt=1,rows=1,interleave=0,gy=0,swap=0,tile=1" is read once per process; aai_debug_axis_tune() replaces it at run time.
-struct AxisTune { int nt = -1, rows = 0, interleave = -1, gy = -1, swap = -1, tile = -1; };
-static AxisTune parse_axis_tune(const char *spec)
-{
-    AxisTune t;
-    if (!spec) return t;
-    auto get = [&](const char *key, int &v) {
-        const char *p = strstr(spec, key);
-        if (p) v = atoi(p + strlen(key));
-    };
-    get("nt=", t.nt); get("rows=", t.rows); get("interleave=", t.interleave); get("gy=", t.gy); get("swap=", t.swap); get("tile=", t.tile);
-    return t;
-}
-static AxisTune &axis_tune()
-{
-    static AxisTune t = parse_axis_tune(experiment_env("AAI_AXIS_TUNE"));
-    return t;
-}
-void set_axis_tune(const char *spec) { axis_tune() = parse_axis_tune(spec); }
-
 template <typename T>
 static hipError_t launch_axis_typed(const AxisLaunch &a, const T *src, ImageView sv, float *dst, ImageView dv,
                                     int batch, hipStream_t stream, const char **kernelName);
@@ -606,8 +568,7 @@ static hipError_t launch_axis_typed(const AxisLaunch &a, const T *src, ImageView
         }
         return hipGetLastError();
     }
-    // Launch shape (see the kernel comment for the measurements behind the defaults).  Each knob can be
-    // overridden for experiments: AAI_AXIS_TUNE="nt=1,rows=1,interleave=0,gy=0".
+    // Launch shape (see the kernel comment for the measurements behind the defaults).
     // Defaults from the sweeps in profiles/r01_axis_tune_*.txt (8192^2 sources):
     //   * windows that share source rows between output rows (grid not pixel-aligned) want cached loads and
     //     two rows per workgroup (5.8 vs 5.2 TB/s at 4:1); disjoint windows want nontemporal loads;
@@ -617,7 +578,7 @@ static hipError_t launch_axis_typed(const AxisLaunch &a, const T *src, ImageView
     //     vs 2.5 at four and 1.4 at one); the up-sampling path (more than 256 outputs per strip) prefers 4;
     //   * 8- and 16-bit sources move 4x / 2x fewer bytes and are bound by per-wave latency, not by HBM: eight / four
     //     rows per workgroup (8192^2 u8 -> 2048^2: 28 us at one row, 21 at eight; profiles/r01_typed_sources.txt).
-    int nt = a.rowsShared ? 0 : 1, interleave = 0, gy = 0, swapXY = 0;
+    int nt = a.rowsShared ? 0 : 1;
     int rows = a.maxRowSpan >= 4 ? (a.rowsShared ? 2 : 1) : 4;
     if (sizeof(T) < 4) {
         // ... as long as that leaves a few workgroups per CU
@@ -634,50 +595,32 @@ static hipError_t launch_axis_typed(const AxisLaunch &a, const T *src, ImageView
     }
     if (!a.transposed && a.maxOutputsPerStrip > 128 && a.maxOutputsPerStrip <= 256) rows = 32;      // ratios below 2: write-heavy
     // the plan's measured choice for this (geometry, device) -- fp32 sources only (aai_engine.cpp: tune_axis_plan)
-    if (sizeof(T) == 4 && a.tuneRows > 0) { rows = a.tuneRows; nt = a.tuneNt; swapXY = a.tuneSwap; }
-    const AxisTune &tune = axis_tune();
-    if (tune.nt >= 0) nt = tune.nt;
-    if (tune.rows > 0) rows = tune.rows;
-    if (tune.interleave >= 0) interleave = tune.interleave;
-    if (tune.gy >= 0) gy = tune.gy;
-    if (tune.swap >= 0) swapXY = tune.swap;
+    if (sizeof(T) == 4 && a.tuneRows > 0) { rows = a.tuneRows; nt = a.tuneNt; }
     // (measured, profiles/r01_axis_transposed.txt: wins below 2:1 -- 1:1 1.8 -> 2.3 TB/s, x4 up-sampling 1.2 -> 1.6 --
     // and loses 5-14 % to the four-column register path between 2:1 and 4:1)
     // ... and, since its output rows run in a software pipeline and its waves store together, down to 64 outputs per strip (ratios up
     // to 4) wherever no output row needs more than the pipeline's eight source rows: 3:1 at 270 degrees 300 -> 242 us per 4 images,
     // 2.5:1 351 -> 271, 2:1 285 -> 275 (profiles/r03_axis_tile.txt)
     const bool tileable = a.transposed && a.tapStep <= 1 && (a.outStrideB == 1 || a.outStrideB == -1) && a.maxOutputsPerStrip <= 256;
-    int tile = tileable && (a.maxOutputsPerStrip > 128 || (a.maxOutputsPerStrip > 64 && a.maxRowSpan <= 8));
-    if (tune.tile == 0) tile = 0;
-    if (tune.tile == 1) tile = tileable && a.maxOutputsPerStrip > 128;      // experiments: the round-1 rule and the independent-waves form
+    const bool tile = tileable && (a.maxOutputsPerStrip > 128 || (a.maxOutputsPerStrip > 64 && a.maxRowSpan <= 8));
     if (tile && (a.nB + kTileCols - 1) / kTileCols <= 65535) {
         // transposed quadrants at ratios below 4: LDS tile, stores along dst x (see aai_axis_tile_kernel)
         if (kernelName) *kernelName = "aai_axis_tile_kernel";
-        const bool coop = tune.tile != 1 && a.nStrips <= 2147483647;      // (experiments: tile=1 keeps the independent-waves form)
-        if (coop) {
-            dim3 grid(a.nStrips, (a.nB + kWaves * kTileCols - 1) / (kWaves * kTileCols), batch), block(kWaves * 64);
-            if (nt) hipLaunchKernelGGL((aai_axis_tile_kernel<true, T, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv);
-            else hipLaunchKernelGGL((aai_axis_tile_kernel<false, T, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv);
-            return hipGetLastError();
-        }
-        dim3 grid((a.nStrips + kWaves - 1) / kWaves, (a.nB + kTileCols - 1) / kTileCols, batch), block(kWaves * 64);
-        if (nt) hipLaunchKernelGGL((aai_axis_tile_kernel<true, T, false>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv);
-        else hipLaunchKernelGGL((aai_axis_tile_kernel<false, T, false>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv);
+        dim3 grid(a.nStrips, (a.nB + kWaves * kTileCols - 1) / (kWaves * kTileCols), batch), block(kWaves * 64);
+        if (nt) hipLaunchKernelGGL((aai_axis_tile_kernel<true, T>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv);
+        else hipLaunchKernelGGL((aai_axis_tile_kernel<false, T>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv);
         return hipGetLastError();
     }
-    const int blocksX = (a.nStrips + kWaves - 1) / kWaves;
     int blocksY = (a.nB + rows - 1) / rows;
-    if (interleave && gy > 0) blocksY = gy < a.nB ? gy : a.nB;
     while (blocksY > 65535) { rows *= 2; blocksY = (a.nB + rows - 1) / rows; }
-    if (swapXY && blocksX > 65535) swapXY = 0;
-    dim3 grid(swapXY ? blocksY : blocksX, swapXY ? blocksX : blocksY, batch), block(kWaves * 64);
+    dim3 grid((a.nStrips + kWaves - 1) / kWaves, blocksY, batch), block(kWaves * 64);
     if (kernelName) *kernelName = "aai_axis_kernel";
     if (a.tapStep > 1) {
-        if (nt) hipLaunchKernelGGL((aai_axis_kernel<true, T, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows, interleave, swapXY);
-        else hipLaunchKernelGGL((aai_axis_kernel<false, T, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows, interleave, swapXY);
+        if (nt) hipLaunchKernelGGL((aai_axis_kernel<true, T, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);
+        else hipLaunchKernelGGL((aai_axis_kernel<false, T, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);
     } else {
-        if (nt) hipLaunchKernelGGL((aai_axis_kernel<true, T, false>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows, interleave, swapXY);
-        else hipLaunchKernelGGL((aai_axis_kernel<false, T, false>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows, interleave, swapXY);
+        if (nt) hipLaunchKernelGGL((aai_axis_kernel<true, T, false>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);
+        else hipLaunchKernelGGL((aai_axis_kernel<false, T, false>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);
     }
     return hipGetLastError();
 }

@@ -300,11 +300,6 @@ int aai_shutdown(void)
     return AAI_OK;
 }
 
-#if defined(AAI_EXPERIMENTS)
-/* experiments build only (tools/tune_axis.py): the run-time form of AAI_AXIS_TUNE; not declared in include/aai.h */
-void aai_debug_axis_tune(const char *spec) { aai::set_axis_tune(spec); }
-#endif
-
 int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)
 {
     if (!d_dst || width < 0 || height < 0 || row0 < 0 || row1 < row0 || row1 > height || stride < width)

@@ -192,7 +192,7 @@ static aai::AxisLaunch make_axis_launch(const Plan &p, int channels, int64_t dst
     a.transposed = t.transposed ? 1 : 0;
     a.tapStep = channels; a.outChan = channels;
     if (channels > 1 && !t.transposed && !t.flipA) { a.outStrideA = 1; a.outChan = 1; }     // lane order = dst element order
-    a.tuneRows = p.tuneRows; a.tuneNt = p.tuneNt; a.tuneSwap = p.tuneSwap;
+    a.tuneRows = p.tuneRows; a.tuneNt = p.tuneNt;
     return a;
 }
 
@@ -211,7 +211,7 @@ struct TuneKey {
         return std::tie(device, rowSpan, rowsShared, widthClass) < std::tie(o.device, o.rowSpan, o.rowsShared, o.widthClass);
     }
 };
-struct TuneShape { int rows, nt, swap; };
+struct TuneShape { int rows, nt; };
 static std::mutex g_tuneMutex;
 static std::map<TuneKey, TuneShape> &tune_cache()
 {
@@ -235,7 +235,7 @@ static void tune_axis_plan(Plan &p, int channels, int band0, hipStream_t stream)
         std::lock_guard<std::mutex> lock(g_tuneMutex);
         auto it = tune_cache().find(key);
         if (it != tune_cache().end()) {
-            p.tuneRows = it->second.rows; p.tuneNt = it->second.nt; p.tuneSwap = it->second.swap; p.tuneSource = 2;
+            p.tuneRows = it->second.rows; p.tuneNt = it->second.nt; p.tuneSource = 2;
             return;
         }
     }
@@ -250,13 +250,13 @@ static void tune_axis_plan(Plan &p, int channels, int band0, hipStream_t stream)
               hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
     for (int b = 0; b < images && ok; ++b)         // realistic data: the memory system's speed depends on what it moves
         ok = aai::launch_synth(src + (size_t)b * g.W * g.H, g.W, g.H, g.W, (uint64_t)b + 1, stream) == hipSuccess;
-    struct Shape { int rows, nt, swap; float ms; };
-    Shape shapes[] = {{1, 1, 0, 0.f}, {2, 1, 0, 0.f}, {1, 0, 0, 0.f}, {2, 0, 0, 0.f}, {4, 1, 0, 0.f}};
+    struct Shape { int rows, nt; float ms; };
+    Shape shapes[] = {{1, 1, 0.f}, {2, 1, 0.f}, {1, 0, 0.f}, {2, 0, 0.f}, {4, 1, 0.f}};
     const aai::ImageView sv{g.W, (int64_t)g.W * g.H}, dv{g.dW, (int64_t)g.dW * g.dH};
     // the shapes take turns, two rounds after a warm-up round, two launches per turn; each keeps its faster turn
     for (int round = 0; round < 3 && ok; ++round)
         for (Shape &sh : shapes) {
-            p.tuneRows = sh.rows; p.tuneNt = sh.nt; p.tuneSwap = sh.swap;
+            p.tuneRows = sh.rows; p.tuneNt = sh.nt;
             const aai::AxisLaunch a = make_axis_launch(p, 1, g.dW);
             float ms = 0.f;
             ok = ok && hipEventRecord(e0, stream) == hipSuccess &&
@@ -265,14 +265,14 @@ static void tune_axis_plan(Plan &p, int channels, int band0, hipStream_t stream)
                  hipEventRecord(e1, stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
             if (ok && round > 0 && (sh.ms == 0.f || ms < sh.ms)) sh.ms = ms;       // round 0 warms up
         }
-    p.tuneRows = 0; p.tuneNt = 0; p.tuneSwap = 0;
+    p.tuneRows = 0; p.tuneNt = 0;
     if (ok) {
         const Shape *best = &shapes[0];
         for (const Shape &sh : shapes)
             if (sh.ms < best->ms * 0.99f) best = &sh;          // a later shape must win by more than the timing noise
-        p.tuneRows = best->rows; p.tuneNt = best->nt; p.tuneSwap = best->swap; p.tuneSource = 1;
+        p.tuneRows = best->rows; p.tuneNt = best->nt; p.tuneSource = 1;
         std::lock_guard<std::mutex> lock(g_tuneMutex);
-        tune_cache()[key] = TuneShape{best->rows, best->nt, best->swap};
+        tune_cache()[key] = TuneShape{best->rows, best->nt};
     }
     (void)hipGetLastError();
     if (e0) (void)hipEventDestroy(e0);
@@ -338,10 +338,9 @@ static int build_plan(Plan &p, hipStream_t bs)
         const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
         // (AAI_MAX_LISTED_PIXELS: test hook, lowers the threshold so that small geometries exercise the dense form)
         static const unsigned maxListed = [] { const char *v = getenv("AAI_MAX_LISTED_PIXELS"); return v ? (unsigned)strtoul(v, nullptr, 10) : kMaxListedPixels; }();      // documented in include/aai.h
-        static const bool classVerify = [] { const char *v = aai::experiment_env("AAI_AXIS_CLASS_VERIFY"); return !(v && atoi(v) == 0); }();
         std::vector<std::pair<int, int>> hostPixels;
         bool hostDense = false;
-        if (verifyAxis && classVerify && aai::axis_verify_by_class(r, hostPixels, hostDense, maxListed)) {
+        if (verifyAxis && aai::axis_verify_by_class(r, hostPixels, hostDense, maxListed)) {
             std::vector<uint2> hostList(hostPixels.size());
             for (size_t i = 0; i < hostPixels.size(); ++i) hostList[i] = make_uint2((unsigned)hostPixels[i].first, (unsigned)hostPixels[i].second);
             // exact arithmetic: one representative per (column class, row class) checked on the host
@@ -494,8 +493,9 @@ std::string plan_description(const aai_request &rq, int channels)
         const bool rotated = p.kernel != AAI_KERNEL_AXIS && p.kernel != AAI_KERNEL_AXIS_WIDE;
         if (p.device == dev && p.band0 < 0 && (rotated || p.channels == channels) && p.built && same_request(p.key, rq)) {
             char buf[256];
-            snprintf(buf, sizeof buf, "kernel=%d rows=%d nt=%d swap=%d tune=%s flagged=%u dense=%d form=%s build_ms=%.3f", p.kernel, p.tuneRows, p.tuneNt,
-                     p.tuneSwap, p.tuneSource == 1 ? "measured" : (p.tuneSource == 2 ? "cached" : "default"), p.flaggedPixels, p.dense ? 1 : 0,
+            // (swap=0: the grid-order field stays in the format that bench.py, the tests and the recorded profiles read)
+            snprintf(buf, sizeof buf, "kernel=%d rows=%d nt=%d swap=0 tune=%s flagged=%u dense=%d form=%s build_ms=%.3f", p.kernel, p.tuneRows, p.tuneNt,
+                     p.tuneSource == 1 ? "measured" : (p.tuneSource == 2 ? "cached" : "default"), p.flaggedPixels, p.dense ? 1 : 0,
                      p.kernel == AAI_KERNEL_ROTATED ? (p.form == aai::ROT_FORM_CELL ? "cell" : "quad") : "-", p.buildMs);
             return std::string(buf);
         }

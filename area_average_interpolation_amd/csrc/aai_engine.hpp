@@ -39,7 +39,7 @@ struct Plan {
     aai::AxisTables tabs;
     aai::AxisEntry *dLane = nullptr, *dRow = nullptr;
     aai::AxisStrip *dStrips = nullptr;
-    int tuneRows = 0, tuneNt = 0, tuneSwap = 0;      // K1 launch shape for this device (0 rows = built-in default)
+    int tuneRows = 0, tuneNt = 0;                     // K1 launch shape for this device (0 rows = built-in default)
     int tuneSource = 0;                               // 0 = built-in default, 1 = measured for this plan, 2 = taken from the per-class cache
     // K2/K3: the dst pixels flagged by the one-off scans (knife edges of the reference's classifier; decisions the fp32
     // kernels leave to double precision) as a list of (dx, dy) the fix-up pass runs over; `dense` when there are
@@ -113,7 +113,7 @@ int require_device();
 // stream that is being captured into a graph is not used), else on the device pool's build stream).
 // form: aai::RotForm of a rotated request's launch (rot_form below); ignored by the other kernels
 int acquire_plan(const aai_request &rq, int band0, int band1, int channels, int form, PlanRef *out, bool onCallerStream = false, hipStream_t stream = nullptr);
-// "kernel=K rows=R nt=N swap=S tune=T flagged=F dense=D form=M build_ms=B" of the cached whole-image plan ("" when there is none)
+// "kernel=K rows=R nt=N swap=0 tune=T flagged=F dense=D form=M build_ms=B" of the cached whole-image plan ("" when there is none)
 std::string plan_description(const aai_request &rq, int channels);
 // which fp32 formulation serves a launch of this request: the cell formulation takes plain images below 4 GiB in area mode
 int rot_form(const aai_request &rq, const Geometry &g, int channels, int srcType, int64_t srcStride);

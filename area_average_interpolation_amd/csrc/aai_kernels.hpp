@@ -11,18 +11,6 @@
 
 namespace aai {
 
-// Launch heuristics can be overridden from the environment for experiments (tools/*_ab.sh) -- only in a build made with
-// `make EXTRA=-DAAI_EXPERIMENTS`: the shipping library never reads these variables.
-inline const char *experiment_env(const char *name)
-{
-#if defined(AAI_EXPERIMENTS)
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
-
 // Image addressing shared by every kernel: element (x,y) of image b is base[b*imageStride + y*rowStride + x].
 // Source element types (AAI_DTYPE_* in include/aai.h).  Outputs are always fp32.
 enum SrcType { SRC_F32 = 0, SRC_U8 = 1, SRC_U16 = 2 };
@@ -50,10 +38,9 @@ struct AxisLaunch {
     int tapStep, outChan;
     int transposed;             // the lane axis runs along dst y (quadrants 1 and 3)
     // launch shape measured by the plan for this (geometry, device): output rows per workgroup (0 = built-in default),
-    // nontemporal source loads, grid order (see aai_axis_kernel)
-    int tuneRows, tuneNt, tuneSwap;
+    // nontemporal source loads (see aai_axis_kernel)
+    int tuneRows, tuneNt;
 };
-void set_axis_tune(const char *spec);      // experiments only (tools/tune_axis.py)
 hipError_t launch_axis(const AxisLaunch &a, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, hipStream_t stream, const char **kernelName);
 
@@ -95,9 +82,6 @@ hipError_t launch_flag_list(const unsigned long long *laneMasks, size_t waves, u
 hipError_t launch_rotated(const RotLaunch &r, const QuadMap &m, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                           int batch, const RotFlags &flags, hipStream_t stream, const char **kernelName);
 bool quad_can_address(const RotLaunch &r, int srcType, ImageView sv);
-// (which form of the kernel family a launch_quad call took, where it has several: a static string, or NULL; per thread)
-void set_quad_kernel_note(const char *note);
-const char *quad_kernel_note();
 hipError_t launch_quad(const RotLaunch &r, const QuadMap &m, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, const unsigned long long *skipMasks, hipStream_t stream, const int *live = nullptr);
 

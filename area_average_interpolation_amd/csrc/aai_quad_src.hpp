@@ -26,12 +26,6 @@ __device__ __forceinline__ void xcd_tile(int band, int &tx, int &ty)
     tx = (int)(j / (unsigned)band);
     ty = (int)((super * 8u + (within & 7u)) * (unsigned)band + j % (unsigned)band);
 }
-// the band height a launcher uses: its default, or AAI_XCD_ROWS in the experiments build
-inline int xcd_band(int dflt)
-{
-    static const int env = [] { const char *e = experiment_env("AAI_XCD_ROWS"); return e ? atoi(e) : -1; }();
-    return env >= 0 ? env : dflt;
-}
 // gridDim.y for `rows` tile rows under xcd_tile; 0: the order cannot be used (more than 65535 rows)
 inline int xcd_grid_rows(int rows, int band)
 {

@@ -27,7 +27,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 
 namespace aai {
 
@@ -412,37 +411,22 @@ hipError_t launch_knife_scan(const RotLaunch &r, unsigned long long *laneMasks, 
     return hipSuccess;
 }
 
-// experiments build only (make exp): AAI_ROT_TUNE="runs=0|1 quad=0|1", read once per process
-struct RotTune { int runs = -1, quad = -1; };
-static const RotTune &rot_tune()
-{
-    static const RotTune t = [] {
-        RotTune v;
-        if (const char *env = experiment_env("AAI_ROT_TUNE")) {
-            if (const char *p = strstr(env, "runs=")) v.runs = atoi(p + 5) != 0;
-            if (const char *p = strstr(env, "quad=")) v.quad = atoi(p + 5) != 0;
-        }
-        return v;
-    }();
-    return t;
-}
-
 // the fp32 quad kernels serve this launch (RotLaunch::quad; area mode: plain and interleaved images; fast mode: plain images)
 static bool quad_serves(const RotLaunch &r, int srcType, ImageView sv)
 {
-    return r.quad && rot_tune().quad != 0 && (r.mode == AAI_MODE_AREA || (r.mode == AAI_MODE_FAST && r.chan == 1)) && quad_can_address(r, srcType, sv);
+    return r.quad && (r.mode == AAI_MODE_AREA || (r.mode == AAI_MODE_FAST && r.chan == 1)) && quad_can_address(r, srcType, sv);
 }
 
 // ... or the cell formulation does: the plan's scan was the cell scan (RotFlags::form) and the launch is one it takes
 static bool cell_serves(const RotLaunch &r, int srcType, ImageView sv, const RotFlags &flags)
 {
-    return flags.form == ROT_FORM_CELL && rot_tune().quad != 0 && cell_can_serve(r, srcType, sv);
+    return flags.form == ROT_FORM_CELL && cell_can_serve(r, srcType, sv);
 }
 
 // ... or, for footprints wider than one 8 x 8 window, the quad formulation split into parts (aai_rotated_wide.hip)
 static bool wide_serves(const RotLaunch &r, int srcType, ImageView sv)
 {
-    return rot_tune().quad != 0 && wide_can_serve(r, srcType, sv);
+    return wide_can_serve(r, srcType, sv);
 }
 
 // one launch of at most 65535 tile rows (16-row tiles; the bicubic sampler: 8-row tiles)
@@ -463,7 +447,6 @@ static hipError_t launch_rotated_band(const RotLaunch &r, const QuadMap &m, cons
         return hipGetLastError();
     }
     dim3 grid((r.dW + 15) / 16, (r.dyEnd - r.dyBase + 15) / 16, batch);
-    const RotTune &tune = rot_tune();
     const bool quad = quad_serves(r, srcType, sv);
     if (cell_serves(r, srcType, sv, flags)) {
         // the cell formulation: one lane per cell of the dst grid, every (dst, src) pair evaluated once
@@ -493,9 +476,7 @@ static hipError_t launch_rotated_band(const RotLaunch &r, const QuadMap &m, cons
     } else if (r.mode == AAI_MODE_FAST && quad) {
         // centres in the dst square, fp32 in the dst frame; flagged pixels belong to the fix-up pass as in area mode
         if (kernelName) *kernelName = "aai_quad_fast_kernel";
-        const hipError_t e = launch_quad(r, m, src, srcType, sv, dst, dv, batch, flags.count ? flags.masks : nullptr, stream, flags.live);
-        if (kernelName && quad_kernel_note()) *kernelName = quad_kernel_note();      // (the LDS-staged form)
-        return e;
+        return launch_quad(r, m, src, srcType, sv, dst, dv, batch, flags.count ? flags.masks : nullptr, stream, flags.live);
     } else if (r.mode == AAI_MODE_FAST) {
         if (kernelName) *kernelName = "aai_rotated_kernel<fast>";
         hipLaunchKernelGGL((aai_rotated_kernel<AAI_MODE_FAST, false, T>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv, nullptr, 0u);
@@ -504,8 +485,7 @@ static hipError_t launch_rotated_band(const RotLaunch &r, const QuadMap &m, cons
         if (kernelName) *kernelName = "aai_quad_kernel<area>";
         return launch_quad(r, m, src, srcType, sv, dst, dv, batch, flags.count ? flags.masks : nullptr, stream, flags.live);
     } else {
-        const int runs = tune.runs >= 0 ? (tune.runs && r.scale == 1) : r.runs;
-        if (runs) {
+        if (r.runs) {
             if (kernelName) *kernelName = "aai_rotated_runs_kernel<area>";
             hipLaunchKernelGGL((aai_rotated_runs_kernel<T, false>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv);
         } else {

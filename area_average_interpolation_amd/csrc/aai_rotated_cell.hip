@@ -17,7 +17,7 @@
 // the source.  16 x 4 tiles cut that to 3.0 M requests (1.46 x, below the quad kernel's 1.8 x) -- and run no faster (222 vs 216
 // us; 5.6 vs 4.4 ms at config 5): the kernel is bound by vector-instruction issue (1.3e8 instructions x ~4 cycles / 1024
 // SIMDs = its duration), the Infinity Cache absorbs the re-reads, and 16-wide rows lose one column in 16 to the halo instead
-// of one in 64.  AAI_CELL_TW=16 at build time (-DAAI_CELL_TILE16) brings the variant back; profiles/r03_cell_kernel.txt.
+// of one in 64.  profiles/r03_cell_kernel.txt.
 //
 // Decisions are left to double precision as in the quad kernel: aai_cell_scan_kernel runs the same code without pixel loads
 // once per geometry and flags every dst pixel fed by a cell with a decision too close to its threshold (or with too little
@@ -26,14 +26,8 @@
 #include "aai_quad_src.hpp"
 #include "aai_rot_cell.hpp"
 
-#include <cstdlib>
-#include <cstring>
-
 // (a cap on the kernel's scalar registers -- 96 would admit a seventh wave per SIMD -- was measured and LOSES: config 3 156 -> 164 us, the
-// spills cost more than the wave brings; -DAAI_CELL_SGPRS=n brings it back; profiles/r04_cell_kernel.txt)
-#ifndef AAI_CELL_SGPRS
-#define AAI_CELL_SGPRS 0
-#endif
+// spills cost more than the wave brings; profiles/r04_cell_kernel.txt)
 namespace aai {
 
 // dst rows a wave walks.  A workgroup of 4 waves pays 4 R + 1 cell rows for 4 R dst rows, so taller is cheaper in instructions --
@@ -44,14 +38,12 @@ namespace aai {
 // SIMD of the chip (1024 SIMDs x ~6 wave slots).
 static int cell_rows_per_wave(int dW, int rows, int batch, double srcRowsPerDstRow, int waveRows = 1)
 {
-    const char *e = experiment_env("AAI_CELL_ROWS");
-    if (e && atoi(e) > 0) return atoi(e);
     const int cols = cell_wave_cols(waveRows);
     const int64_t strips = ((int64_t)dW + cols - 1) / cols * batch;
     int R;
     int64_t floorWaves = 24576;
     if (waveRows == 2) {
-        // the 32 x 2 wave (ratios from 2:1 up; us per image, tools/cell_wave_ab.sh): 16 rows up to config 3's ratio (one image 174 / 154 /
+        // the 32 x 2 wave (ratios from 2:1 up; us per image): 16 rows up to config 3's ratio (one image 174 / 154 /
         // 147 at 4 / 8 / 16 rows; 8 images per launch 150 / 133 / 130; 2:1 at 30 degrees 290 / 275 / 273 at 8 / 16 / 32), 8 rows from
         // ~2.7:1 up (3:1 at 30 degrees 281 / 323 / 342 at 8 / 16 / 32; 4:1 at 45: 184 / 210 / 251; 5:1 at 17.5: 189 / 214 / 240)
         R = srcRowsPerDstRow < 2.7 ? 16 : 8;
@@ -265,9 +257,9 @@ __device__ __forceinline__ void cell_segment(int blockY0, int blockY1, int rowsP
 
 // WR: the wave's shape (cell_wave_rows): 1 = 64 cell columns x 1 cell row per step, 2 = 32 x 2
 template <typename T, int WIN, bool SCALED, bool HP, int WR>
-__global__ __launch_bounds__(kQuadBlock, cell_min_waves(WIN)) __attribute__((amdgpu_num_sgpr(AAI_CELL_SGPRS))) void aai_cell_kernel(
+__global__ __launch_bounds__(kQuadBlock, cell_min_waves(WIN)) void aai_cell_kernel(
     RotLaunch r, QuadConsts<float> q, CellConsts<float> z, CellLive live, QuadMap m, const T *__restrict__ src, ImageView sv, float *__restrict__ dst, ImageView dv,
-    const unsigned long long *__restrict__ skipMasks, int tilesX, int rowsPerWave, int bigBlocks, int tailRows, int xcdRows, int rowBlocks)
+    const unsigned long long *__restrict__ skipMasks, int tilesX, int rowsPerWave, int xcdRows, int rowBlocks)
 {
     constexpr int kCellLanes = cell_wave_lanes(WR), kCellCols = cell_wave_cols(WR);
     __shared__ float window[WIN * WIN][kQuadBlock];
@@ -281,14 +273,11 @@ __global__ __launch_bounds__(kQuadBlock, cell_min_waves(WIN)) __attribute__((amd
     xcd_tile(xcdRows, bx, by);
     if (by >= rowBlocks) return;                               // (block-uniform; rows the padded grid adds)
     const int x0 = bx * kCellCols;                             // (block-uniform: every wave reaches the walk's barrier)
-    // the last workgroups of a launch are shorter (tailRows rows per wave instead of rowsPerWave): the waves that finish it live a
-    // fraction as long, and the chip drains in a fraction of the time
-    const int rpw = by < bigBlocks ? rowsPerWave : tailRows;
-    const int blockY0 = r.dyBase + (by < bigBlocks ? by * (kCellWaves * rowsPerWave) : bigBlocks * (kCellWaves * rowsPerWave) + (by - bigBlocks) * (kCellWaves * tailRows));
-    const int blockY1 = min(blockY0 + kCellWaves * rpw, r.dyEnd);
+    const int blockY0 = r.dyBase + by * (kCellWaves * rowsPerWave);
+    const int blockY1 = min(blockY0 + kCellWaves * rowsPerWave, r.dyEnd);
     int y0, y1;
     bool ownsBottom;
-    cell_segment(blockY0, blockY1, rpw, wave, y0, y1, ownsBottom);           // dst rows [y0, y1); cell rows y0 .. y1
+    cell_segment(blockY0, blockY1, rowsPerWave, wave, y0, y1, ownsBottom);   // dst rows [y0, y1); cell rows y0 .. y1
     float *image = dst + (int64_t)blockIdx.z * dv.imageStride;
     const char *img = reinterpret_cast<const char *>(src + (int64_t)blockIdx.z * sv.imageStride + m.base);
     const CellColumn col = cell_column(r, z, min(x0 + (lane & (kCellLanes - 1)), r.dW));      // (cell_walk: lanes beyond column dW repeat it)
@@ -457,43 +446,24 @@ hipError_t launch_cell_tile(const RotLaunch &r, const QuadConsts<float> &q, cons
                             float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
 {
     const int rows = r.dyEnd - r.dyBase;
-    // the wave's shape (cell_wave_rows; experiments build: AAI_CELL_WAVE=1 / 2)
-    int waveRows = cell_wave_rows(r.side, m.scale, r.c, r.s);
-    {
-        const char *e = experiment_env("AAI_CELL_WAVE");
-        if (e && m.scale <= 1 && (atoi(e) == 1 || atoi(e) == 2 || atoi(e) == 4)) waveRows = atoi(e);      // (4: 16 x 4, experiments build only)
-    }
+    const int waveRows = cell_wave_rows(r.side, m.scale, r.c, r.s);      // the wave's shape
     const int rowsPerWave = cell_rows_per_wave(r.dW, rows, batch, r.side / (m.scale > 0 ? m.scale : 1), waveRows);
     const int strips = (r.dW + cell_wave_cols(waveRows) - 1) / cell_wave_cols(waveRows);
-    const int blockRows = kCellWaves * rowsPerWave;
     // (Shorter segments for the last rows of a launch -- waves that live half as long, so that the chip drains sooner -- paid with
-    // 8-row strips per wave; with four waves per strip segment they measure nothing: config 3 160.7 us without, 161.0 ... 166.3 with.
-    // Experiments (-DAAI_EXPERIMENTS): AAI_CELL_TAIL="<percent of the rows>,<rows per wave in the tail>".)
-    int tailPct = 0, tailR = 2;
-    {
-        const char *e = experiment_env("AAI_CELL_TAIL");
-        if (e) { tailPct = atoi(e); const char *c = strchr(e, ','); tailR = c ? atoi(c + 1) : 2; }
-    }
-    int bigBlocks = (rows + blockRows - 1) / blockRows, tailRows = rowsPerWave, tailBlocks = 0;
-    if (tailPct > 0 && tailR > 0 && tailR < rowsPerWave) {
-        bigBlocks = (int)((int64_t)rows * (100 - tailPct) / 100 / blockRows);
-        tailRows = tailR;
-        tailBlocks = (rows - bigBlocks * blockRows + kCellWaves * tailRows - 1) / (kCellWaves * tailRows);
-        if (bigBlocks + tailBlocks > 65535) { bigBlocks = (rows + blockRows - 1) / blockRows; tailRows = rowsPerWave; tailBlocks = 0; }      // grid.y
-    }
-    const int rowBlocks = bigBlocks + tailBlocks;
+    // 8-row strips per wave; with four waves per strip segment they measure nothing: config 3 160.7 us without, 161.0 ... 166.3 with.)
+    const int rowBlocks = (rows + kCellWaves * rowsPerWave - 1) / (kCellWaves * rowsPerWave);
     // XCD-aware workgroup order: config 3 is bound by instruction issue and does not move (170.0 us at 0 / 1 / 2 / 4 row blocks per
     // band), but geometries whose waves wait for memory do: 2:1 at 45 degrees 312 -> 275 / 260 / 257 us, 4:1 at 30 degrees 275 -> 270;
     // replicated sources (config 5: one source row feeds four dst rows) lose 1-4 % beyond one block and gain nothing: off there.
-    // (profiles/r04_fast_xcd.txt; experiments build: AAI_XCD_ROWS.)
-    const int band = xcd_band(m.scale > 1 ? 0 : kCellXcdRowsDefault);
+    // (profiles/r04_fast_xcd.txt)
+    const int band = m.scale > 1 ? 0 : kCellXcdRowsDefault;
     const int gy = xcd_grid_rows(rowBlocks, band);
     const int xcdRows = gy ? band : 0;
     const dim3 grid(strips, gy ? gy : rowBlocks, batch);
     const int tilesX = (r.dW + 15) / 16;
     const CellLive live = make_cell_live(r, z);
 #define AAI_CELL_LAUNCH(SCALED, HP, WR) \
-    hipLaunchKernelGGL((aai_cell_kernel<T, WIN, SCALED, HP, WR>), grid, dim3(kQuadBlock), 0, stream, r, q, z, live, m, src, sv, dst, dv, skipMasks, tilesX, rowsPerWave, bigBlocks, tailRows, xcdRows, rowBlocks)
+    hipLaunchKernelGGL((aai_cell_kernel<T, WIN, SCALED, HP, WR>), grid, dim3(kQuadBlock), 0, stream, r, q, z, live, m, src, sv, dst, dv, skipMasks, tilesX, rowsPerWave, xcdRows, rowBlocks)
     if ((q.hiPrec != 0) != (HPSEL == 1) && HPSEL != 2) return hipErrorInvalidValue;       // (the dispatcher picks the unit that holds the variant)
     if (m.scale > 1) {                                          // (replicated sources: the 64 x 1 wave only)
         if (HPSEL != 0 && q.hiPrec) AAI_CELL_LAUNCH(true, true, 1);
@@ -501,11 +471,6 @@ hipError_t launch_cell_tile(const RotLaunch &r, const QuadConsts<float> &q, cons
     } else if (waveRows == 2) {
         if (HPSEL != 0 && q.hiPrec) AAI_CELL_LAUNCH(false, true, 2);
         if (HPSEL != 1 && !q.hiPrec) AAI_CELL_LAUNCH(false, false, 2);
-#if defined(AAI_EXPERIMENTS)
-    } else if (waveRows == 4) {
-        if (HPSEL != 0 && q.hiPrec) AAI_CELL_LAUNCH(false, true, 4);
-        if (HPSEL != 1 && !q.hiPrec) AAI_CELL_LAUNCH(false, false, 4);
-#endif
     } else {
         if (HPSEL != 0 && q.hiPrec) AAI_CELL_LAUNCH(false, true, 1);
         if (HPSEL != 1 && !q.hiPrec) AAI_CELL_LAUNCH(false, false, 1);
@@ -545,7 +510,7 @@ hipError_t launch_cell_multi_words(const RotLaunch &r, const QuadConsts<float> &
         const int rowsPerWave = cell_rows_per_wave(r.dW, rows, batch, r.side / (m.scale > 0 ? m.scale : 1));
         const int strips = (r.dW + cell_wave_cols(1) - 1) / cell_wave_cols(1);
         const int rowBlocks = (rows + kCellWaves * rowsPerWave - 1) / (kCellWaves * rowsPerWave);
-        const int band = xcd_band(m.scale > 1 ? 0 : kCellXcdRowsDefault);
+        const int band = m.scale > 1 ? 0 : kCellXcdRowsDefault;
         const int gy = xcd_grid_rows(rowBlocks, band);
         const int xcdRows = gy ? band : 0;
         const dim3 grid(strips, gy ? gy : rowBlocks, batch);
@@ -667,8 +632,7 @@ hipError_t launch_cell_multi_u16(const RotLaunch &r, const QuadMap &m, const uns
 bool cell_can_serve(const RotLaunch &r, int srcType, ImageView sv)
 {
     // plain images below 4 GiB (lanes address their pixels with unsigned 32-bit byte offsets from the image's first element)
-    static const bool enabled = [] { const char *e = experiment_env("AAI_CELL"); return !(e && atoi(e) == 0); }();      // experiments: AAI_CELL=0 keeps the quad kernel
-    if (!enabled || !r.cell || r.mode != AAI_MODE_AREA) return false;
+    if (!r.cell || r.mode != AAI_MODE_AREA) return false;
     // Small outputs stay on the quad kernel: a cell wave lives for rows + 1 cell rows, and an image of fewer than ~1000 such
     // waves (about 720 x 720 dst pixels) cannot fill the chip with them -- the reference's own example call (158 x 158 dst
     // pixels at 5.9 : 1) takes 71 us on 60 cell waves and 36 us on 390 one-shot quad waves.

@@ -273,8 +273,7 @@ AAI_WIDE_ENTRY(launch_wide_u16, unsigned short) { return launch_wide_typed<unsig
 #if !defined(AAI_WIDE_PART) || AAI_WIDE_PART == 1
 bool wide_can_serve(const RotLaunch &r, int srcType, ImageView sv)
 {
-    static const bool off = [] { const char *e = experiment_env("AAI_WIDE"); return e && atoi(e) == 0; }();      // experiments: AAI_WIDE=0 keeps the runs kernel
-    if (off || !r.wide || (r.mode != AAI_MODE_AREA && r.mode != AAI_MODE_FAST) || r.chan != 1 || r.scale != 1 || (r.dyBase & 15) != 0) return false;
+    if (!r.wide || (r.mode != AAI_MODE_AREA && r.mode != AAI_MODE_FAST) || r.chan != 1 || r.scale != 1 || (r.dyBase & 15) != 0) return false;
     // (tilesX * 16 blocks along grid.x)
     if ((int64_t)((r.dW + 15) / 16) * 16 > 2147483647ll) return false;
     return quad_can_address(r, srcType, sv);

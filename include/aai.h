@@ -172,8 +172,7 @@ int aai_prepare(const aai_request *req, int32_t channels /* 1 for plain images; 
  * All of it runs on a private stream and blocks only the calling thread: plans of other requests, devices and threads are
  * built and launched from concurrently.
  *
- * Environment variables the shipping library reads (all of them; launch-heuristic overrides exist only in the experiments build,
- * `make -C area_average_interpolation_amd/csrc exp`):
+ * Environment variables the library reads (all of them):
  *   AAI_AXIS_AUTOTUNE=0      no launch-shape measurement for K1 (built-in shape), see above
  *   AAI_MAX_LISTED_PIXELS=n  a plan whose scans list more than n pixels (default 16 M) hands the WHOLE image to the double-precision
  *                            pass instead of keeping the list (`dense` in aai_plan_info); results are the same either way, only the
@@ -181,8 +180,8 @@ int aai_prepare(const aai_request *req, int32_t channels /* 1 for plain images; 
  *   AAI_TRACE_PLAN=1         stage timings of every plan build on stderr
  *
  * aai_plan_info writes a one-line description of the cached whole-image plan of `req` on the current device into `text`
- * ("" when there is none yet): "kernel=K rows=R nt=N swap=S tune=measured|cached|default flagged=F dense=D form=cell|quad|-
- * build_ms=B" -- the kernel family (AAI_KERNEL_*), K1's launch shape and where it came from, the dst pixels the
+ * ("" when there is none yet): "kernel=K rows=R nt=N swap=0 tune=measured|cached|default flagged=F dense=D form=cell|quad|-
+ * build_ms=B" -- the kernel family (AAI_KERNEL_*), K1's launch shape (swap is always 0) and where it came from, the dst pixels the
  * double-precision pass owns, the fp32 formulation of a rotated area request, and what building the plan cost. */
 int aai_plan_info(const aai_request *req, int32_t channels, char *text, int32_t capacity);
 /* Drops every cached plan (device tables, flag lists, side streams) while the HIP runtime is alive.  Optional: the cache is

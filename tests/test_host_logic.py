@@ -113,7 +113,7 @@ def test_nonfinite_and_oversize_arguments_are_rejected(aai):
 def test_the_library_has_no_process_wide_debug_switches(aai):
     """Round 3 shipped three exported globals that steered the library for every caller of the process (aai_debug_skip_fixup -- which
     switched the correctness pass off --, aai_debug_cell_min_waves, aai_debug_axis_tune) and eleven launch-heuristic getenv switches.
-    They are per-request policy bits now (include/aai.h) or exist in the experiments build only."""
+    They are per-request policy bits now (include/aai.h) or gone: the launch heuristics are fixed in the source."""
     import ctypes
     from area_average_interpolation_amd import _lib as L
     lib = ctypes.CDLL(L.LIB_PATH)
@@ -121,7 +121,7 @@ def test_the_library_has_no_process_wide_debug_switches(aai):
         assert not hasattr(lib, name), name
     blob = open(L.LIB_PATH, "rb").read()
     for env in (b"AAI_CELL_ROWS", b"AAI_CELL_TAIL", b"AAI_CELL\0", b"AAI_WIDE\0", b"AAI_FAST_ROWS", b"AAI_ROT_TUNE", b"AAI_AXIS_TUNE", b"AAI_AXIS_CLASS_VERIFY",
-                b"AAI_FAST_LDS"):
+                b"AAI_FAST_LDS", b"AAI_XCD_ROWS", b"AAI_CELL_WAVE"):
         assert env not in blob, env
     for env in (b"AAI_AXIS_AUTOTUNE", b"AAI_MAX_LISTED_PIXELS", b"AAI_TRACE_PLAN"):      # the three include/aai.h documents
         assert env in blob, env
@@ -736,8 +736,8 @@ def test_band_source_rows_hold_what_every_kernel_family_fetches(aai, hostemu):
 
 
 def test_staged_tile_boxes_hold_every_window_of_their_tile(aai, hostemu):
-    """aai_quad_fast_lds_kernel stages the box of each 16 x 16 dst tile in LDS (fast_tile_box, aai_rot_quad.hpp) and its lanes read
-    their windows from it: every lattice position of every window (quad_fast_pixel's own arithmetic, through a recording source) must
+    """An LDS-staged fast-mode kernel (measured, not shipped: profiles/r04_fast_lds.txt) stages the box of each 16 x 16 dst tile
+    (fast_tile_box, aai_rot_quad.hpp) and its lanes read their windows from it: every lattice position of every window (quad_fast_pixel's own arithmetic, through a recording source) must
     lie inside its tile's box, and no box may exceed the side the LDS pitch is sized for.  All quadrants, ratios 1:1 ... 5:1."""
     import ctypes
     rng = np.random.default_rng(17)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the one-off plan creation (tables, launch-shape measurement, model / knife / fp32-margin scans) per BASELINE geometry:
 aai_prepare cold (first plan of its class in this process), then a second geometry of the same class (warm launch-shape
-cache), then the same request again (cached plan).  usage: [AAI_AXIS_AUTOTUNE=0] [AAI_AXIS_CLASS_VERIFY=0] python tools/plan_time.py"""
+cache), then the same request again (cached plan).  usage: [AAI_AXIS_AUTOTUNE=0] python tools/plan_time.py"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -42,7 +42,7 @@ for (sr, ang, mode) in ((2.0, 0.0, 1), (2.0, 90.0, 1), (3.0, 17.5, 1), (3.0, 17.
 aai.debug_cell_min_waves(-1)
 torch.cuda.synchronize()
 print("first touch of every kernel family (code objects loaded): %.1f ms" % (1e3 * (time.perf_counter() - t0)))
-print("AAI_AXIS_AUTOTUNE=%s AAI_AXIS_CLASS_VERIFY=%s" % (os.environ.get("AAI_AXIS_AUTOTUNE", "1"), os.environ.get("AAI_AXIS_CLASS_VERIFY", "1")))
+print("AAI_AXIS_AUTOTUNE=%s" % os.environ.get("AAI_AXIS_AUTOTUNE", "1"))
 prep("cfg2 8192^2 -> 2048^2 @0 (cold class)", 8192, 8192, 4.0, 1.0, 0.0, 1)
 prep("8192x8000 4:1 @0 (same class, warm tune cache)", 8192, 8000, 4.0, 1.0, 0.0, 1)
 prep("cfg2 @180 (same class, warm)", 8192, 8192, 4.0, 1.0, 180.0, 1)

@@ -80,6 +80,8 @@ SYMBOLS = {
     "aai_resample_batch_host": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, ctypes.c_int32, _I64, _I64, _P, _I64, _I64, _LY]),
     "aai_band_source_rows": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "aai_resample_band_device_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _P, _I64, _P]),
+    "aai_adjoint_batch_device_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_adjoint_f32": (ctypes.c_int, [_RQ, _P, _I64, _P, _I64, _LY]),
     "aai_synth_device_f32": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _I64, ctypes.c_uint64, _P]),
     "aai_synth_rows_device_f32": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _I64, ctypes.c_uint64, _P]),
     "aai_prepare": (ctypes.c_int, [_RQ, ctypes.c_int32]),

@@ -277,6 +277,37 @@ def resample_device(request, src_ptr, src_stride, dst_ptr, dst_stride, stream=0,
         raise AaiError(rc, last_error())
 
 
+def adjoint_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None,
+                   dst_image_stride=0, src_image_stride=0):
+    """aai_adjoint_batch_device_f32: gsrc = W(request)^T gdst on device-resident fp32 images -- the transpose of what
+    resample_device computes (area and fast modes).  Raw device pointers (ints), strides in elements, a hipStream_t handle;
+    every element of the src_width x src_height gradient image is written."""
+    rc = L.load().aai_adjoint_batch_device_f32(_ref(request), 1 if batch is None else int(batch), gdst_ptr, dst_stride, dst_image_stride,
+                                               gsrc_ptr, src_stride, src_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def adjoint_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle,
+                 mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
+    """Host-buffer adjoint (aai_adjoint_f32): gdst is the [dH, dW] gradient with respect to the output of
+    resample_host(src of shape src_shape = (H, W), ...); returns (code, message, gsrc [H, W] float32 or None)."""
+    lib = L.load()
+    H, W = int(src_shape[0]), int(src_shape[1])
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None
+    g = np.ascontiguousarray(gdst, dtype=np.float32)
+    if g.shape != (lay.dst_height, lay.dst_width):
+        raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width),))
+    gsrc = np.empty((H, W), dtype=np.float32)
+    rc = lib.aai_adjoint_f32(_ref(rq), g.ctypes.data, max(lay.dst_width, 1), gsrc.ctypes.data, W, None)
+    if rc != L.OK:
+        return rc, last_error(), None
+    return rc, "", gsrc
+
+
 def resample_multi_device(request, shards, src_stride, src_image_stride, dst_stride, dst_image_stride):
     """aai_resample_batch_multi_device_f32: `shards` is a list of (device, count, src_ptr, dst_ptr, stream) -- one batch of
     independent images spread over several GPUs of this process, no collective."""

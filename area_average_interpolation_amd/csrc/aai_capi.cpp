@@ -300,6 +300,54 @@ int aai_shutdown(void)
     return AAI_OK;
 }
 
+int aai_adjoint_batch_device_f32(const aai_request *req, int32_t batch,
+                                 const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                 float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    // argument errors are reported before the device is touched
+    aai::Geometry g;
+    int rc = check_adjoint(req, batch, d_gdst, dst_stride, d_gsrc, src_stride, g);
+    if (rc != AAI_OK) return rc;
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    rc = require_device();
+    if (rc != AAI_OK) return rc;
+    rc = enqueue_adjoint(*req, g, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream);
+    if (rc == AAI_OK) g_lastError.clear();
+    return rc;
+}
+
+int aai_adjoint_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    int rc = check_adjoint(req, 1, gdst, dst_stride, gsrc, src_stride, g);
+    if (rc != AAI_OK) return rc;
+    rc = require_device();
+    if (rc != AAI_OK) return rc;
+    float *dGdst = nullptr, *dGsrc = nullptr;
+    hipStream_t stream = nullptr;
+    auto cleanup = [&]() {
+        if (dGdst) (void)hipFree(dGdst);
+        if (dGsrc) (void)hipFree(dGsrc);
+    };
+#define AAI_HIP_C(call)                                                        \
+    do {                                                                       \
+        hipError_t e__ = (call);                                               \
+        if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #call); }     \
+    } while (0)
+    AAI_HIP_C(hipMalloc((void **)&dGdst, sizeof(float) * (size_t)g.dW * g.dH));
+    AAI_HIP_C(hipMalloc((void **)&dGsrc, sizeof(float) * (size_t)g.W * g.H));
+    AAI_HIP_C(hipMemcpy2D(dGdst, sizeof(float) * g.dW, gdst, sizeof(float) * dst_stride, sizeof(float) * g.dW, g.dH, hipMemcpyHostToDevice));
+    rc = enqueue_adjoint(*req, g, 1, dGdst, g.dW, 0, dGsrc, g.W, 0, stream);
+    if (rc != AAI_OK) { cleanup(); return rc; }
+    AAI_HIP_C(hipStreamSynchronize(stream));
+    AAI_HIP_C(hipMemcpy2D(gsrc, sizeof(float) * src_stride, dGsrc, sizeof(float) * g.W, sizeof(float) * g.W, g.H, hipMemcpyDeviceToHost));
+    cleanup();
+#undef AAI_HIP_C
+    if (layout) fill_layout(g, resolved_kernel(*req, g), layout);
+    g_lastError.clear();
+    return AAI_OK;
+}
+
 int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)
 {
     if (!d_dst || width < 0 || height < 0 || row0 < 0 || row1 < row0 || row1 > height || stride < width)

@@ -107,6 +107,7 @@ void drop_plans()
             if (pool.join[k]) { (void)hipEventDestroy(pool.join[k]); pool.join[k] = nullptr; }
         }
         pool.sideReady = false; pool.sideFailed = false; pool.besideLaunches = 0;
+        if (pool.scratch) { (void)hipMemPoolDestroy(pool.scratch); pool.scratch = nullptr; }      // (its memory goes once the frees in flight have run)
     }
     if (current >= 0) (void)hipSetDevice(current);
 }
@@ -586,6 +587,63 @@ int enqueue(const aai_request &rq, int batch, const void *dSrc, int srcType, int
     }
     g_lastKernel = name;
     if (e != hipSuccess) return hip_fail(e, name);
+    return AAI_OK;
+}
+
+int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride, Geometry &g)
+{
+    int rc = check_request(rq);
+    if (rc != AAI_OK) return rc;
+    if (batch < 0) return fail(AAI_ERR_BAD_ARGUMENT, "Negative batch.");
+    std::string msg;
+    rc = aai::make_geometry(*rq, g, msg);
+    if (rc != AAI_OK) return fail(rc, msg);
+    if (rq->mode == AAI_MODE_BILINEAR) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BILINEAR: the area and fast modes only.");
+    if (rq->mode == AAI_MODE_BICUBIC) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BICUBIC: the area and fast modes only.");
+    if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the adjoint.");
+    if (!gdst || !gsrc) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
+    if (srcStride < g.W) return fail(AAI_ERR_BAD_ARGUMENT, "Source stride smaller than the image width.");
+    if (dstStride < g.dW) return fail(AAI_ERR_BAD_ARGUMENT, "Destination stride smaller than the output width.");
+    return AAI_OK;
+}
+
+int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
+                    float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+{
+    // (AAI_POLICY_DOUBLE_PRECISION / AAI_POLICY_PREFER_CELL choose between forward kernels; the adjoint has one, in double precision)
+    const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
+    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
+    // scratch: one fp64 image of the dst size per image in flight; large batches go through in chunks of about 1 GiB of it
+    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * sizeof(double);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch, kMaxGridZ), ((size_t)1 << 30) / imageBytes));
+    int device = 0;
+    AAI_HIP(hipGetDevice(&device));
+    hipMemPool_t scratch = nullptr;
+    {
+        DevicePool &pool = device_pool(device);
+        std::lock_guard<std::mutex> lock(pool.m);
+        if (!pool.scratch) {
+            hipMemPoolProps props{};
+            props.allocType = hipMemAllocationTypePinned;
+            props.location.type = hipMemLocationTypeDevice;
+            props.location.id = device;
+            AAI_HIP(hipMemPoolCreate(&pool.scratch, &props));
+            uint64_t keep = UINT64_MAX;
+            const hipError_t ea = hipMemPoolSetAttribute(pool.scratch, hipMemPoolAttrReleaseThreshold, &keep);
+            if (ea != hipSuccess) { (void)hipMemPoolDestroy(pool.scratch); pool.scratch = nullptr; return hip_fail(ea, "hipMemPoolSetAttribute"); }
+        }
+        scratch = pool.scratch;
+    }
+    double *n = nullptr;
+    AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
+    const char *name = "";
+    hipError_t e = hipSuccess;
+    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk)
+        e = aai::launch_adjoint(r, std::min(batch - b0, chunk), dGdst + (int64_t)b0 * dstImageStride, dv, n, dGsrc + (int64_t)b0 * srcImageStride, sv, stream, &name);
+    const hipError_t ef = hipFreeAsync(n, stream);
+    g_lastKernel = name;
+    if (e != hipSuccess) return hip_fail(e, name);
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     return AAI_OK;
 }
 

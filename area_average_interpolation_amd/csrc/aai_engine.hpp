@@ -91,6 +91,11 @@ struct DevicePool {
     hipEvent_t fork[kSideSlots] = {}, join[kSideSlots] = {};
     bool sideReady = false, sideFailed = false;
     unsigned besideLaunches = 0, nextSide = 0;
+    // the adjoint's scratch (enqueue_adjoint): a memory pool of the library's own, created on the first adjoint call of the device.
+    // It keeps what it has been given (release threshold: everything), so that after the first call of a size an allocation is
+    // stream-ordered bookkeeping and never a trip to the driver -- the device's default pool hands its memory back at every
+    // synchronisation.  aai_shutdown destroys it.
+    hipMemPool_t scratch = nullptr;
 };
 DevicePool &device_pool(int device);      // (heap, never destroyed; aai_shutdown releases the streams while the runtime is alive)
 
@@ -122,6 +127,13 @@ int rot_form(const aai_request &rq, const Geometry &g, int channels, int srcType
 int enqueue(const aai_request &rq, int batch, const void *dSrc, int srcType, int64_t srcStride, int64_t srcImageStride,
             float *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream, int band0 = -1, int band1 = -1,
             int channels = 1);
+
+// The adjoint of an area / fast request: argument checks that need no device (mode, policy, batch, geometry, pointers, strides) ...
+int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride, Geometry &g);
+// ... and the two launches on `stream`, with stream-ordered scratch from the device pool's memory pool (hipMallocFromPoolAsync /
+// hipFreeAsync on `stream`): no plan, nothing blocks.  Strides in elements.
+int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
+                    float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 
 }  // namespace engine
 }  // namespace aai

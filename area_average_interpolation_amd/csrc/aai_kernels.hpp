@@ -99,6 +99,11 @@ hipError_t launch_cell_scan(const RotLaunch &r, unsigned long long *laneMasks, u
 hipError_t launch_cell(const RotLaunch &r, const QuadMap &m, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, const unsigned long long *skipMasks, hipStream_t stream);
 
+// ---- the adjoint of the area / fast modes (aai_adjoint.hip): gsrc = W^T gdst, double precision, every angle ------------
+// `batch` <= 65535 images; n = scratch of batch x dH x dW doubles (pass 1 writes it, pass 2 gathers from it)
+hipError_t launch_adjoint(const RotLaunch &r, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
+                          hipStream_t stream, const char **kernelName);
+
 // ---- utilities -----------------------------------------------------------------------------------------
 hipError_t launch_synth(float *dst, int W, int H, int64_t stride, uint64_t seed, hipStream_t stream);
 hipError_t launch_synth_rows(float *dst, int W, int H, int row0, int row1, int64_t stride, uint64_t seed, hipStream_t stream);

@@ -1,0 +1,79 @@
+"""The resampling as a differentiable torch operator.
+
+``resample(x, ...)`` runs the library's forward (aai_resample_batch_device_f32) on a device-resident fp32 tensor and is a
+``torch.autograd.Function``: its backward is the library's adjoint (aai_adjoint_batch_device_f32), gsrc = W^T gdst with the
+forward's own weights -- not an approximation through ``grid_sample``.  Both launch on ``torch.cuda.current_stream()`` of the
+tensor's device and only enqueue work.
+
+torch is imported here, not by the package: ``import area_average_interpolation_amd`` works without it.
+"""
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib as L
+from . import api
+
+
+def _ensure_prepared(rq):
+    """The forward's first call per (geometry, device) builds a plan and synchronises (aai_prepare): do that now, outside
+    any stream capture.  Inside a capture an unprepared geometry is an error, not a hidden synchronisation."""
+    if api.plan_shape(rq):
+        return
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("resample(): this geometry has no plan on this device yet and the current stream is being captured; "
+                           "call resample() (or prepare()) once with the same geometry before capturing")
+    api.prepare(rq)
+
+
+class _Resample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rq, lay):
+        B, H, W = x.shape
+        y = torch.empty((B, lay.dst_height, lay.dst_width), dtype=torch.float32, device=x.device)
+        ctx.rq, ctx.src_shape = rq, (B, H, W)
+        if B:
+            with torch.cuda.device(x.device):
+                _ensure_prepared(rq)
+                api.resample_device(rq, x.data_ptr(), W, y.data_ptr(), lay.dst_width, stream=torch.cuda.current_stream().cuda_stream,
+                                    batch=B, src_image_stride=H * W, dst_image_stride=lay.dst_height * lay.dst_width)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        B, H, W = ctx.src_shape
+        gy = gy.contiguous()
+        if gy.dtype != torch.float32:
+            gy = gy.float()
+        gx = torch.empty((B, H, W), dtype=torch.float32, device=gy.device)
+        if B:
+            dH, dW = gy.shape[1], gy.shape[2]
+            with torch.cuda.device(gy.device):
+                api.adjoint_device(ctx.rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
+                                   batch=B, dst_image_stride=dH * dW, src_image_stride=H * W)
+        return gx, None, None
+
+
+def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
+    """Resample a CUDA/HIP fp32 tensor of shape (H, W) or (B, H, W); returns ``(y, dst_isocenter)`` with y of shape
+    (dH, dW) or (B, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
+    bilinear / bicubic comparison paths have no adjoint: an x that requires grad raises ValueError there).  Non-contiguous
+    input is made contiguous; other dtypes raise TypeError, CPU tensors and other ranks ValueError, an invalid geometry
+    AaiError."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("resample() takes a torch.Tensor")
+    if x.dtype != torch.float32:
+        raise TypeError("resample() takes a float32 tensor, got %s" % x.dtype)
+    if not x.is_cuda:
+        raise ValueError("resample() takes a tensor on a GPU (the library has no CPU path)")
+    if x.dim() not in (2, 3):
+        raise ValueError("resample() takes a tensor of shape (H, W) or (B, H, W)")
+    xb = (x if x.dim() == 3 else x.unsqueeze(0)).contiguous()
+    rq = api.make_request(xb.shape[2], xb.shape[1], src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = api.query(rq)
+    if rc != L.OK:
+        raise api.AaiError(rc, msg)
+    if xb.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
+        raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
+    y = _Resample.apply(xb, rq, lay)
+    return (y if x.dim() == 3 else y.squeeze(0)), (lay.dst_iso_x, lay.dst_iso_y)

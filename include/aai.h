@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 #define AAI_VERSION_MAJOR 0
-#define AAI_VERSION_MINOR 1
+#define AAI_VERSION_MINOR 2
 
 /* ---- status codes ------------------------------------------------------------------------- */
 enum {
@@ -253,6 +253,52 @@ int aai_resample_batch_host(const aai_request *req, int32_t batch, const void *s
 int aai_band_source_rows(const aai_request *req, int32_t dst_row0, int32_t dst_row1, int32_t *src_row0, int32_t *src_row1);
 int aai_resample_band_device_f32(const aai_request *req, int32_t dst_row0, int32_t dst_row1,
                                  const float *d_src_rows, int64_t src_stride, float *d_dst_rows, int64_t dst_stride, void *stream);
+
+/* ---- the adjoint (transposed) resampling: gradients through the area and fast modes ------------------------------------
+ * A request in AAI_MODE_AREA or AAI_MODE_FAST is a linear map of the source image, dst = W src, with W[d, s] = the weight
+ * of source pixel s in dst pixel d (overlap area / the dst pixel's total overlap; 1 / count in fast mode; a dst pixel the
+ * forward writes 0 to is a zero row) -- the matrix aai_resample_device_f32 applies, under AAI_POLICY_REFERENCE or
+ * AAI_POLICY_EXACT as requested.  These calls apply its TRANSPOSE:
+ *
+ *     gsrc[s] = sum over d of W[d, s] * gdst[d]      for EVERY pixel s of the src_width x src_height image
+ *
+ * which is what the gradient step of anything that optimises through the resampling needs (the reference has no such
+ * call).  gdst has the forward's output size (aai_query), gsrc the request's source size; source pixels no dst pixel reads
+ * get 0.0 written, so the caller never clears gsrc.  With integer pre-expansion (layout.scale > 1) a source pixel's value is
+ * the sum over its scale^2 virtual pixels.  fp32 in, fp32 out, single channel.
+ *   - Modes: AAI_MODE_BILINEAR / AAI_MODE_BICUBIC are refused (AAI_ERR_BAD_ARGUMENT, the message names the mode).
+ *     AAI_POLICY_DOUBLE_PRECISION and AAI_POLICY_PREFER_CELL are accepted and change nothing; AAI_POLICY_DIAG_NO_FIXUP is
+ *     refused.  Arguments are validated like aai_query validates them, before the device is touched.
+ *   - Weights: every (dst, src) pair is evaluated in double precision by the per-pair code of the forward's fix-up pass,
+ *     the replay of the reference's classifier at knife edges included; sums in double precision, ONE fp32 rounding of the
+ *     result (~6e-8 relative).  One code path for every rotation: multiples of 90 degrees, where the separable kernel
+ *     serves the forward, go through the same general kernels and are correspondingly slower than they could be.
+ *   - Cost: two kernels -- one lane per dst pixel (gdst / its total weight, into scratch), then one lane per SOURCE pixel
+ *     that gathers from the dst pixels it feeds.  Each evaluates every overlapping pair once, with the knife-edge variant of
+ *     the per-pair code for EVERY pair.  MEASURED on an MI355X (profiles/adjoint_time.txt, per kernel: profiles/
+ *     adjoint_trace.txt): 5 to 15 times the forward under AAI_POLICY_DOUBLE_PRECISION at general angles -- 8192^2 -> 3426^2 at
+ *     17.5 degrees: 7.5 ms in area mode (forward 0.70 ms), 1.5 ms in fast mode (0.13 ms); the gather is ~3/4 of it -- and
+ *     13 to 350 times the forward at multiples of 90 degrees, where the forward is the separable streaming kernel.  The
+ *     worst case is an exactly grid-aligned geometry at reduced angle 0 (4096^2 -> 1024^2 at 4:1: 7.0 ms against 0.02 ms):
+ *     there every dst edge runs along pixel boundaries, so nearly every boundary pair sits on a knife edge of the classifier
+ *     and goes through the slow replay of the reference's arithmetic.  Plan for these figures, not for the 2 x a count of
+ *     pair evaluations suggests.
+ *   - Determinism: a gather, no atomics, a fixed summation order: the same inputs give the same bits, and image b of a
+ *     batch gets the bits of a single-image call.
+ *   - No plan is built (aai_prepare and aai_plan_info are not involved): the geometry block is recomputed on the host per
+ *     call.  The device call takes its scratch -- one fp64 image of the dst size per image, batches beyond ~1 GiB of it in
+ *     chunks -- stream-ordered (hipMallocFromPoolAsync / hipFreeAsync on the caller's stream) from a memory pool of the
+ *     library's own, one per device, created by the first adjoint call on that device and told to keep its memory: the first
+ *     call of a size asks the driver for it, later calls only do stream-ordered bookkeeping.  The call only enqueues and
+ *     never synchronises.  aai_shutdown destroys the pool.  Whether the call can be recorded into a stream capture (it
+ *     would need the runtime to capture stream-ordered allocations) is UNTESTED: do not rely on it.
+ * aai_last_kernel() names the gather kernel afterwards. */
+int aai_adjoint_batch_device_f32(const aai_request *req, int32_t batch,
+                                 const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                 float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream);
+/* host buffers: upload gdst, run, download gsrc; `layout` may be NULL */
+int aai_adjoint_f32(const aai_request *req, const float *gdst, int64_t dst_stride,
+                    float *gsrc, int64_t src_stride, aai_layout *layout);
 
 /* ---- synthetic input ------------------------------------------------------------
  * Fill a device image with the stateless-hash fp32 uniform [0,1) pattern used by every benchmark and

@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Time the adjoint (aai_adjoint_batch_device_f32) next to the forward under AAI_POLICY_DOUBLE_PRECISION -- the shipped code that
+does the same double-precision pair evaluations once per pair -- on the geometries of the adjoint identity test, both modes.
+A fresh child process per geometry; in it 3 warm-up launches of each, then N (default 24) timed launches of each between
+device events, forward and adjoint alternating; reported: median, 10th..90th percentile, and the ratio of the medians.
+
+usage: python tools/adjoint_time.py [--launches N] [--out FILE]      (the table also goes to stdout)"""
+import argparse
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+# (name, W, H, srcRes, dstRes, angle)
+GEOMETRIES = [("cfg3", 8192, 8192, 8192.0, 2731.0, 17.5), ("wide8", 8192, 8192, 8.0, 1.0, 17.5), ("up2", 2048, 2048, 1.0, 2.0, 30.0),
+              ("axis4", 4096, 4096, 4.0, 1.0, 0.0), ("quarter2.5", 4096, 4096, 2.5, 1.0, 90.0)]
+
+
+def child(name, mode, launches):
+    import numpy as np
+    import torch
+    import area_average_interpolation_amd as aai
+    aai.set_device(0)
+    _, W, H, sr, dr, ang = [g for g in GEOMETRIES if g[0] == name][0]
+    iso = ((W - 1) / 2, (H - 1) / 2)
+    adj = aai.make_request(W, H, sr, dr, iso, ang, mode=mode)
+    fwd = aai.make_request(W, H, sr, dr, iso, ang, mode=mode, policy=aai.POLICY_REFERENCE | aai.POLICY_DOUBLE_PRECISION)
+    lay = aai.query(adj)[2]
+    dW, dH = lay.dst_width, lay.dst_height
+    st = torch.cuda.current_stream().cuda_stream
+    x = torch.empty((H, W), dtype=torch.float32, device="cuda")
+    y = torch.empty((dH, dW), dtype=torch.float32, device="cuda")
+    aai.synth_device(x.data_ptr(), W, H, W, 1, st)
+    aai.synth_device(y.data_ptr(), dW, dH, dW, 2, st)
+    wx, wty = torch.empty_like(y), torch.empty_like(x)
+    aai.prepare(fwd)
+
+    def run_fwd():
+        aai.resample_device(fwd, x.data_ptr(), W, wx.data_ptr(), dW, st)
+
+    def run_adj():
+        aai.adjoint_device(adj, y.data_ptr(), dW, wty.data_ptr(), W, st)
+
+    for _ in range(3):
+        run_fwd()
+        run_adj()
+    torch.cuda.synchronize()
+    fwd_kernel = ""
+    times = {"fwd": [], "adj": []}
+    for _ in range(launches):
+        for key, fn in (("fwd", run_fwd), ("adj", run_adj)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[key].append(a.elapsed_time(b))
+            if key == "fwd":
+                fwd_kernel = aai.last_kernel()
+    f, a = np.array(times["fwd"]), np.array(times["adj"])
+    print("%-10s %-4s %5dx%-5d -> %5dx%-5d  forward fp64 %8.3f ms (%.3f..%.3f)  adjoint %8.3f ms (%.3f..%.3f)  ratio %5.2f  [%s]" % (
+        name, "area" if mode == aai.MODE_AREA else "fast", W, H, dW, dH,
+        np.median(f), np.percentile(f, 10), np.percentile(f, 90), np.median(a), np.percentile(a, 10), np.percentile(a, 90),
+        np.median(a) / np.median(f), fwd_kernel.split("(")[0].strip()), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launches", type=int, default=24)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", nargs=2, default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.launches < 20:
+        ap.error("at least 20 timed launches")
+    if args.child:
+        child(args.child[0], int(args.child[1]), args.launches)
+        return 0
+    lines = ["# median (10th..90th percentile) of %d launches each, device events, forward and adjoint alternating, one process per row" % args.launches]
+    print(lines[0], flush=True)
+    for g in GEOMETRIES:
+        for mode in (1, 2):
+            # a fresh process per row, under its own time limit; a row that fails ends the run
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--launches", str(args.launches), "--child", g[0], str(mode)],
+                               capture_output=True, text=True, timeout=240)
+            if r.returncode != 0:
+                sys.stderr.write(r.stdout + r.stderr)
+                return r.returncode or 1
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith(g[0])][-1]
+            print(line, flush=True)
+            lines.append(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

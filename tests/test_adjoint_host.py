@@ -1,6 +1,7 @@
 """The adjoint (transposed) resampling, checks that need no GPU: ABI, argument errors before any device call, the package's
 lazy torch import, the source-word rules of the new files, and a serial CPU replay of the kernels' per-pixel bodies
-(tests/emulation/adjoint_emulation.cpp over csrc/aai_adjoint_math.hpp) against the oracle's matrix."""
+(tests/emulation/adjoint_emulation.cpp over csrc/aai_adjoint_math.hpp) against the oracle's matrix, and, at sizes the matrix cannot
+reach, against columns of it taken from comb images (tests/adjoint_columns.py)."""
 import ctypes
 import json
 import os
@@ -189,3 +190,79 @@ def test_cpu_replay_on_knife_edge_geometries(aai, po, adjemu, knife_golden, axis
                 got = adjemu(aai.make_request(c["W"], c["H"], c["src_res"], c["dst_res"], tuple(c["iso"]), c["angle"], mode=mode), g)
                 assert_adjoint_matches(got, gold, "replay knife %d mode %d" % (i, mode))
         assert ran >= 12
+
+
+# ---- per-pixel gold at sizes the matrix cannot reach: comb images (tests/adjoint_columns.py) ----
+# (name, W, H, srcRes, dstRes, angle, isocenter offset from the image centre, mode, policy, number of phases)
+COMB_CASES = [
+    ("3:1 area", 300, 220, 3, 1, 17.5, (0, 0), "area", 0, 4), ("3:1 fast", 300, 220, 3, 1, 17.5, (0, 0), "fast", 0, 4),
+    ("1:3 q1", 90, 70, 1, 3, 117.5, (0, 0), "area", 0, 4), ("4:1 axis", 256, 256, 4, 1, 0.0, (0, 0), "area", 0, 4),
+    ("8:1 q2", 200, 260, 8, 1, 200.25, (0, 0), "area", 0, 4), ("2:1 45", 128, 128, 2, 1, 45.0, (0, 0), "area", 0, 4),
+    # near-axis pair
+    ("near 0", 180, 150, 3, 1, 1e-7, (0, 0), "area", 0, 4), ("near 90", 180, 150, 3, 1, 89.9999999, (0, 0), "area", 0, 4),
+    # scale >= 3 up-sampling in each quadrant (adjoint_virtual_pixel's four branches), both modes between them
+    ("1:2 q0", 70, 54, 1, 2, 30.0, (0, 0), "area", 0, 4), ("1:2 q1", 54, 70, 1, 2, 107.5, (0.3, -0.2), "fast", 0, 4),
+    ("1:3 q2", 60, 44, 1, 3, 200.25, (0, 0), "fast", 0, 4), ("1:2 q3", 58, 66, 1, 2, 305.0, (0, 0), "area", 0, 4),
+    ("40:1", 420, 380, 40, 1, 17.5, (0, 0), "area", 0, 4), ("40:1 fast", 420, 380, 40, 1, 17.5, (0, 0), "fast", 0, 2),
+    ("iso outside", 150, 130, 3, 1, 17.5, (-240.0, 170.0), "area", 0, 4), ("iso outside q2 up", 50, 60, 1, 2, 215.0, (90.0, -75.0), "area", 0, 4),
+    ("exact policy", 300, 220, 3, 1, 17.5, (0, 0), "area", 1, 4), ("exact policy 1:1", 140, 120, 1, 1, 30.0, (0.3, -0.2), "area", 1, 4),
+    ("1500 x 1200", 1500, 1200, 3, 1, 17.5, (0, 0), "area", 0, 2), ("1600 x 1300 fast", 1600, 1300, 3, 1, 107.5, (0, 0), "fast", 0, 2),
+]
+
+
+def corner_phases(W, H, pitch, count):
+    """phases by index: column 0 / row 0, the last column / last row, then column 0 with the last row and the last column with row 0"""
+    a, b = (W - 1) % pitch, (H - 1) % pitch
+    out = []
+    for ph in ((0, 0), (a, b), (0, b), (a, 0), (pitch // 2, pitch // 2), (1, pitch - 1)):
+        if ph not in out:
+            out.append(ph)
+    return out[:count]
+
+
+def comb_case_gold(po, aai, case, seed=7):
+    """(rq, gdst fp32, sx, sy, gold) of a COMB_CASES entry"""
+    from adjoint_columns import comb_cases, comb_pitch
+    name, W, H, sr, dr, ang, off, mode, policy, phases = case
+    mode = aai.MODE_FAST if mode == "fast" else aai.MODE_AREA
+    iso = ((W - 1) / 2 + off[0], (H - 1) / 2 + off[1])
+    rq = aai.make_request(W, H, sr, dr, iso, ang, mode=mode, policy=policy)
+    rc, msg, lay = aai.query(rq)
+    assert rc == 0, msg
+    g = np.random.default_rng(seed).random((lay.dst_height, lay.dst_width)).astype(np.float32)
+    pitch = comb_pitch(lay, ang)
+    phs = corner_phases(W, H, pitch, phases)
+    assert len(phs) == phases and phs[0] == (0, 0) and phs[1] == ((W - 1) % pitch, (H - 1) % pitch)
+    sx, sy, gold = comb_cases(po, po.MODE_FAST if mode == aai.MODE_FAST else po.MODE_EXACT, W, H, sr, dr, iso, ang, policy, g, phs, pitch)
+    # row 0, column 0, the last row and the last column are among the pixels, and the samples are not all in unread corners
+    assert (sx == 0).any() and (sy == 0).any() and (sx == W - 1).any() and (sy == H - 1).any()
+    assert sx.size >= phases * (W // pitch) * (H // pitch) and 4 * int((gold != 0).sum()) >= sx.size
+    return rq, g, sx, sy, gold
+
+
+@pytest.mark.parametrize("case", COMB_CASES, ids=[c[0] for c in COMB_CASES])
+def test_cpu_replay_matches_comb_gold(aai, po, adjemu, case):
+    """the replay of the kernels' per-pixel bodies against columns of the oracle's matrix taken from comb images: images up to
+    1600 x 1300, coordinates up to 1600, footprints up to 40:1, every quadrant of a replicated (scale >= 3) source"""
+    rq, g, sx, sy, gold = comb_case_gold(po, aai, case)
+    got = adjemu(rq, g)
+    assert_adjoint_matches(got[sy, sx], gold, "replay comb %s (%d source pixels)" % (case[0], sx.size))
+
+
+def test_pixel_list_comb_equals_the_full_comb(aai, po, adjemu):
+    """the pixel-list form of the comb (oracle_pixels on candidates from conftest.sample_points: what the GPU suite uses at size) gives
+    the full form's gold, adjacent pixels and every quadrant included"""
+    from adjoint_columns import comb_gold_pixels
+    for case in (COMB_CASES[0], COMB_CASES[1], COMB_CASES[4], COMB_CASES[8], COMB_CASES[9], COMB_CASES[10], COMB_CASES[11], COMB_CASES[14]):
+        rq, g, sx, sy, gold = comb_case_gold(po, aai, case[:9] + (2,))
+        lay = aai.query(rq)[2]
+        pick = np.arange(0, sx.size, max(1, sx.size // 150))
+        omode = po.MODE_FAST if rq.mode == aai.MODE_FAST else po.MODE_EXACT
+        listed, n = comb_gold_pixels(po, omode, rq, lay, lambda dx, dy: g[dy, dx], sx[pick], sy[pick])
+        assert n > 0 and np.array_equal(listed, gold[pick]), case[0]
+        # a 4 x 4 block of adjacent pixels in a corner and one in the middle: split over comb images, same bar as the full comb
+        W, H = rq.src_width, rq.src_height
+        bx, by = [a.ravel() for a in np.meshgrid(np.arange(4), np.arange(4))]
+        bx, by = np.concatenate([W - 4 + bx, W // 2 + bx]), np.concatenate([H - 4 + by, H // 2 + by])
+        block, _ = comb_gold_pixels(po, omode, rq, lay, lambda dx, dy: g[dy, dx], bx, by)
+        assert_adjoint_matches(adjemu(rq, g)[by, bx], block, "replay pixel-list comb %s" % case[0])

@@ -21,215 +21,151 @@
 
 using namespace aai::engine;
 
-// Host-buffer convenience path: H2D, one launch, D2H.  T is float or double (converted on the device).
-template <typename T>
-int resample_host(const aai_request *req, const T *src, int64_t srcStride, T *dst, int64_t dstStride, aai_layout *layout)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    aai::Geometry g;
-    std::string msg;
-    rc = aai::make_geometry(*req, g, msg);
-    if (rc != AAI_OK) return fail(rc, msg);
-    if (!src || !dst) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
-    if (srcStride < g.W) return fail(AAI_ERR_BAD_ARGUMENT, "Source stride smaller than the image width.");
-    if (dstStride < g.dW) return fail(AAI_ERR_BAD_ARGUMENT, "Destination stride smaller than the output width.");
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
+namespace {
 
-    const size_t nSrc = (size_t)g.W * g.H, nDst = (size_t)g.dW * g.dH;
-    T *dSrcT = nullptr, *dDstT = nullptr;
-    float *dSrc = nullptr, *dDst = nullptr;
-    hipStream_t stream = nullptr;
-    auto cleanup = [&]() {
-        if (dSrcT) (void)hipFree(dSrcT);
-        if (dDstT && (void *)dDstT != (void *)dDst) (void)hipFree(dDstT);
-        if (dSrc && (void *)dSrc != (void *)dSrcT) (void)hipFree(dSrc);
-        if (dDst) (void)hipFree(dDst);
-    };
-#define AAI_HIP_C(call)                                                        \
-    do {                                                                       \
-        hipError_t e__ = (call);                                               \
-        if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #call); }     \
+// ---- argument checks ---------------------------------------------------------------------------------------
+// An entry point reads as the list of its checks: each returns AAI_OK or records its text and returns its code, and the
+// first that fails ends the call.  Argument errors come before the device is touched, like the reference reports them
+// first; the ORDER of an entry point's checks is what a caller with two faults sees and is pinned, entry point by entry
+// point, by tests/test_entry_point_errors.py -- which is why check_request and request_geometry are two calls: most
+// entry points report a bad element type, channel count or batch between the two.
+#define AAI_TRY(check)                              \
+    do {                                            \
+        const int rc__ = (check);                   \
+        if (rc__ != AAI_OK) return rc__;            \
     } while (0)
 
-    AAI_HIP_C(hipMalloc((void **)&dSrcT, sizeof(T) * nSrc));
-    AAI_HIP_C(hipMemcpy2D(dSrcT, sizeof(T) * g.W, src, sizeof(T) * srcStride, sizeof(T) * g.W, g.H, hipMemcpyHostToDevice));
-    if (nDst) AAI_HIP_C(hipMalloc((void **)&dDst, sizeof(float) * nDst));
-    if (sizeof(T) == sizeof(float)) {
-        dSrc = reinterpret_cast<float *>(dSrcT);
-        dDstT = reinterpret_cast<T *>(dDst);
-    } else {
-        AAI_HIP_C(hipMalloc((void **)&dSrc, sizeof(float) * nSrc));
-        AAI_HIP_C(aai::launch_f64_to_f32(reinterpret_cast<const double *>(dSrcT), dSrc, nSrc, stream));
-        if (nDst) AAI_HIP_C(hipMalloc((void **)&dDstT, sizeof(T) * nDst));
+int request_geometry(const aai_request &rq, aai::Geometry &g)      // the reference's validation and everything derived from the request
+{
+    std::string msg;
+    const int rc = aai::make_geometry(rq, g, msg);
+    return rc == AAI_OK ? AAI_OK : fail(rc, msg);
+}
+
+int check_dtype(int32_t dtype)
+{
+    if (dtype != AAI_DTYPE_F32 && dtype != AAI_DTYPE_U8 && dtype != AAI_DTYPE_U16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown source element type.");
+    return AAI_OK;
+}
+
+int check_channels(int32_t channels)
+{
+    return channels < 1 || channels > 4 ? fail(AAI_ERR_BAD_ARGUMENT, "Channels must be 1..4.") : AAI_OK;
+}
+
+int check_batch(int32_t batch)      // any size: enqueue() splits batches beyond the grid.z limit
+{
+    return batch < 0 ? fail(AAI_ERR_BAD_ARGUMENT, "Negative batch.") : AAI_OK;
+}
+
+int check_pointers(const void *a, const void *b)
+{
+    return !a || !b ? fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.") : AAI_OK;
+}
+
+// interleaved images: the kernels index the elements of a row with 32-bit integers
+int check_row_length(const aai::Geometry &g, int channels)
+{
+    if ((int64_t)g.W * channels > INT32_MAX / 2 || (int64_t)g.dW * channels > INT32_MAX / 2) return fail(AAI_ERR_TOO_LARGE, "Image too large.");
+    return AAI_OK;
+}
+
+// strides in elements; an interleaved pixel takes `channels` of them
+int check_strides(const aai::Geometry &g, int channels, int64_t srcStride, int64_t dstStride)
+{
+    if (srcStride < (int64_t)g.W * channels) return fail(AAI_ERR_BAD_ARGUMENT, "Source stride smaller than the image width.");
+    if (dstStride < (int64_t)g.dW * channels) return fail(AAI_ERR_BAD_ARGUMENT, "Destination stride smaller than the output width.");
+    return AAI_OK;
+}
+
+// The adjoint of an area / fast request: the argument checks of both entries, none of which needs a device
+int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride, aai::Geometry &g)
+{
+    AAI_TRY(check_request(rq));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(request_geometry(*rq, g));
+    if (rq->mode == AAI_MODE_BILINEAR) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BILINEAR: the area and fast modes only.");
+    if (rq->mode == AAI_MODE_BICUBIC) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BICUBIC: the area and fast modes only.");
+    if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the adjoint.");
+    AAI_TRY(check_pointers(gdst, gsrc));
+    return check_strides(g, 1, srcStride, dstStride);
+}
+
+int finish(const aai_request &rq, const aai::Geometry &g, aai_layout *layout)
+{
+    if (layout) fill_layout(g, resolved_kernel(rq, g), layout);
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+// ---- host-buffer paths -------------------------------------------------------------------------------------
+// a hipMalloc allocation that frees itself (move-only)
+struct DeviceBuffer {
+    void *p = nullptr;
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { std::swap(p, o.p); return *this; }
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }      // (no padding: every kernel clamps its vector loads into the image)
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+// dense device rows <-> strided host rows; sizes in elements of `esz` bytes
+hipError_t upload(const DeviceBuffer &d, const void *h, int64_t hStride, int64_t row, int rows, size_t esz)
+{
+    return hipMemcpy2D(d.p, esz * row, h, esz * hStride, esz * row, rows, hipMemcpyHostToDevice);
+}
+hipError_t download(void *h, int64_t hStride, const DeviceBuffer &d, int64_t row, int rows, size_t esz)
+{
+    return hipMemcpy2D(h, esz * hStride, d.p, esz * row, esz * row, rows, hipMemcpyDeviceToHost);
+}
+
+// The host round trip behind aai_resample_f32 / _f64 / _host / _interleaved_host, the caller's checks done: upload, one launch on
+// the null stream, download.  srcType: AAI_DTYPE_* of the host source; f64: host source AND destination are doubles instead,
+// converted to and from fp32 on the device.  Strides in elements.
+int host_round_trip(const aai_request &rq, const aai::Geometry &g, int channels, int srcType, bool f64, const void *src, int64_t srcStride,
+                    void *dst, int64_t dstStride, aai_layout *layout)
+{
+    const int64_t rowIn = (int64_t)g.W * channels, rowOut = (int64_t)g.dW * channels;      // elements per dense row
+    const size_t nSrc = (size_t)rowIn * g.H, nDst = (size_t)rowOut * g.dH;
+    const size_t inSize = f64 ? sizeof(double) : aai::src_elem_size(srcType), outSize = f64 ? sizeof(double) : sizeof(float);
+    hipStream_t stream = nullptr;
+    DeviceBuffer in, out, in32, out64;      // in32 / out64: the fp32 source and the fp64 result of a double-precision call
+    AAI_HIP(in.alloc(inSize * nSrc));
+    AAI_HIP(upload(in, src, srcStride, rowIn, g.H, inSize));
+    if (nDst) AAI_HIP(out.alloc(sizeof(float) * nDst));
+    if (f64) {
+        AAI_HIP(in32.alloc(sizeof(float) * nSrc));
+        AAI_HIP(aai::launch_f64_to_f32(in.as<const double>(), in32.as<float>(), nSrc, stream));
+        if (nDst) AAI_HIP(out64.alloc(sizeof(double) * nDst));
     }
     if (nDst) {
-        rc = enqueue(*req, 1, dSrc, aai::SRC_F32, g.W, 0, dDst, g.dW, 0, stream);
-        if (rc != AAI_OK) { cleanup(); return rc; }
-        if (sizeof(T) != sizeof(float))
-            AAI_HIP_C(aai::launch_f32_to_f64(dDst, reinterpret_cast<double *>(dDstT), nDst, stream));
-        AAI_HIP_C(hipStreamSynchronize(stream));
-        AAI_HIP_C(hipMemcpy2D(dst, sizeof(T) * dstStride, dDstT, sizeof(T) * g.dW, sizeof(T) * g.dW, g.dH, hipMemcpyDeviceToHost));
+        AAI_TRY(enqueue(rq, g, 1, f64 ? in32.p : in.p, f64 ? (int)aai::SRC_F32 : srcType, rowIn, 0, out.as<float>(), rowOut, 0, stream, -1, -1, channels));
+        if (f64) AAI_HIP(aai::launch_f32_to_f64(out.as<const float>(), out64.as<double>(), nDst, stream));
+        AAI_HIP(hipStreamSynchronize(stream));
+        AAI_HIP(download(dst, dstStride, f64 ? out64 : out, rowOut, g.dH, outSize));
     }
-    cleanup();
-#undef AAI_HIP_C
-    if (layout) fill_layout(g, resolved_kernel(*req, g), layout);
-    g_lastError.clear();
-    return AAI_OK;
+    return finish(rq, g, layout);
 }
 
-extern "C" {
-
-int aai_version(void) { return AAI_VERSION_MAJOR * 1000 + AAI_VERSION_MINOR; }
-
-const char *aai_last_error(void) { return g_lastError.c_str(); }
-
-const char *aai_last_kernel(void) { return g_lastKernel.c_str(); }
-
-const char *aai_error_string(int code)
+// aai_resample_f32 / aai_resample_f64
+int resample_host_plain(const aai_request *req, bool f64, const void *src, int64_t srcStride, void *dst, int64_t dstStride, aai_layout *layout)
 {
-    switch (code) {
-    case AAI_OK: return "";
-    case AAI_ERR_RESOLUTION_MISMATCH: return "Assumed X & Y resolution are same.";
-    case AAI_ERR_RESOLUTION_NONPOSITIVE: return "0 or negative resolution is not acceptable.";
-    case AAI_ERR_NO_ROWS: return "There is no data in src array.";
-    case AAI_ERR_NO_COLUMNS: return "There is no data in the second dimension of src array.";
-    case AAI_ERR_NONFINITE: return "Non-finite argument.";
-    case AAI_ERR_BAD_ARGUMENT: return "Bad argument.";
-    case AAI_ERR_TOO_LARGE: return "Image too large.";
-    case AAI_ERR_NO_DEVICE: return "No HIP device available.";
-    case AAI_ERR_HIP: return "HIP runtime error.";
-    case AAI_ERR_EMPTY_OUTPUT: return "Output image would be empty.";
-    default: return "Unknown error.";
-    }
-}
-
-int aai_query(const aai_request *req, aai_layout *out)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    if (!out) return fail(AAI_ERR_BAD_ARGUMENT, "Null layout.");
     aai::Geometry g;
-    std::string msg;
-    rc = aai::make_geometry(*req, g, msg);
-    if (rc != AAI_OK) return fail(rc, msg);
-    fill_layout(g, resolved_kernel(*req, g), out);
-    g_lastError.clear();
-    return AAI_OK;
+    AAI_TRY(check_request(req));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_pointers(src, dst));
+    AAI_TRY(check_strides(g, 1, srcStride, dstStride));
+    AAI_TRY(require_device());
+    return host_round_trip(*req, g, 1, AAI_DTYPE_F32, f64, src, srcStride, dst, dstStride, layout);
 }
 
-int aai_device_count(int *count)
+// validates the request and a dst row band; the source rows the band reads
+int band_source_rows(const aai_request *req, int32_t dst_row0, int32_t dst_row1, int32_t *src_row0, int32_t *src_row1, aai::Geometry &g)
 {
-    if (!count) return fail(AAI_ERR_BAD_ARGUMENT, "Null count.");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) { (void)hipGetLastError(); n = 0; }
-    *count = n;
-    return AAI_OK;
-}
-
-int aai_set_device(int ordinal)
-{
-    int rc = require_device();
-    if (rc != AAI_OK) return rc;
-    AAI_HIP(hipSetDevice(ordinal));
-    return AAI_OK;
-}
-
-int aai_device_synchronize(void)
-{
-    int rc = require_device();
-    if (rc != AAI_OK) return rc;
-    AAI_HIP(hipDeviceSynchronize());
-    return AAI_OK;
-}
-
-static int resample_batch_device_typed(const aai_request *req, int32_t batch, const void *d_src, int32_t src_dtype,
-                                       int64_t src_stride, int64_t src_image_stride,
-                                       float *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    if (src_dtype != AAI_DTYPE_F32 && src_dtype != AAI_DTYPE_U8 && src_dtype != AAI_DTYPE_U16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown source element type.");
-    if (batch < 0) return fail(AAI_ERR_BAD_ARGUMENT, "Negative batch.");      // any size: enqueue() splits batches beyond the grid.z limit
-    // argument errors are reported before the device is touched, like the reference reports them first
-    {
-        aai::Geometry g;
-        std::string msg;
-        rc = aai::make_geometry(*req, g, msg);
-        if (rc != AAI_OK) return fail(rc, msg);
-    }
-    if (!d_src || !d_dst) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    rc = enqueue(*req, batch, d_src, src_dtype, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream);
-    if (rc == AAI_OK) g_lastError.clear();
-    return rc;
-}
-
-int aai_resample_batch_device_f32(const aai_request *req, int32_t batch,
-                                  const float *d_src, int64_t src_stride, int64_t src_image_stride,
-                                  float *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
-{
-    return resample_batch_device_typed(req, batch, d_src, AAI_DTYPE_F32, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, stream);
-}
-
-int aai_resample_batch_device(const aai_request *req, int32_t batch, const void *d_src, int32_t src_dtype,
-                              int64_t src_stride, int64_t src_image_stride,
-                              float *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
-{
-    return resample_batch_device_typed(req, batch, d_src, src_dtype, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, stream);
-}
-
-int aai_resample_batch_multi_device_f32(const aai_request *req, int32_t n_shards, const int32_t *devices, const int32_t *counts,
-                                        const float *const *d_src, int64_t src_stride, int64_t src_image_stride,
-                                        float *const *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *const *streams)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    if (n_shards < 0 || (n_shards > 0 && (!devices || !counts || !d_src || !d_dst))) return fail(AAI_ERR_BAD_ARGUMENT, "Bad shard description.");
-    {
-        aai::Geometry g;
-        std::string msg;
-        rc = aai::make_geometry(*req, g, msg);
-        if (rc != AAI_OK) return fail(rc, msg);
-    }
-    for (int i = 0; i < n_shards; ++i) {
-        if (counts[i] < 0) return fail(AAI_ERR_BAD_ARGUMENT, "Negative batch.");
-        if (counts[i] > 0 && (!d_src[i] || !d_dst[i])) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
-    }
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    int home = 0;
-    AAI_HIP(hipGetDevice(&home));
-    for (int i = 0; i < n_shards && rc == AAI_OK; ++i) {
-        if (counts[i] == 0) continue;
-        const hipError_t e = hipSetDevice(devices[i]);
-        if (e != hipSuccess) { rc = hip_fail(e, "hipSetDevice"); break; }
-        rc = enqueue(*req, counts[i], d_src[i], aai::SRC_F32, src_stride, src_image_stride, d_dst[i], dst_stride, dst_image_stride,
-                     streams ? (hipStream_t)streams[i] : nullptr);
-    }
-    (void)hipSetDevice(home);
-    if (rc == AAI_OK) g_lastError.clear();
-    return rc;
-}
-
-int aai_resample_device_f32(const aai_request *req, const float *d_src, int64_t src_stride,
-                            float *d_dst, int64_t dst_stride, void *stream)
-{
-    return aai_resample_batch_device_f32(req, 1, d_src, src_stride, 0, d_dst, dst_stride, 0, stream);
-}
-
-int aai_band_source_rows(const aai_request *req, int32_t dst_row0, int32_t dst_row1, int32_t *src_row0, int32_t *src_row1)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
+    AAI_TRY(check_request(req));
     if (!src_row0 || !src_row1) return fail(AAI_ERR_BAD_ARGUMENT, "Null output pointer.");
-    aai::Geometry g;
-    std::string msg;
-    rc = aai::make_geometry(*req, g, msg);
-    if (rc != AAI_OK) return fail(rc, msg);
+    AAI_TRY(request_geometry(*req, g));
     if (dst_row0 < 0 || dst_row1 > g.dH || dst_row0 >= dst_row1) return fail(AAI_ERR_BAD_ARGUMENT, "Band rows out of range.");
     const int kernel = pick_kernel(*req, g);
     int a = 0, b = g.H;
@@ -245,253 +181,6 @@ int aai_band_source_rows(const aai_request *req, int32_t dst_row0, int32_t dst_r
     g_lastError.clear();
     return AAI_OK;
 }
-
-int aai_resample_band_device_f32(const aai_request *req, int32_t dst_row0, int32_t dst_row1,
-                                 const float *d_src_rows, int64_t src_stride, float *d_dst_rows, int64_t dst_stride, void *stream)
-{
-    int32_t a, b;
-    int rc = aai_band_source_rows(req, dst_row0, dst_row1, &a, &b);      // validates request and band
-    if (rc != AAI_OK) return rc;
-    if (!d_src_rows || !d_dst_rows) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    rc = enqueue(*req, 1, d_src_rows, aai::SRC_F32, src_stride, 0, d_dst_rows, dst_stride, 0, (hipStream_t)stream, dst_row0, dst_row1);
-    if (rc == AAI_OK) g_lastError.clear();
-    return rc;
-}
-
-int aai_prepare(const aai_request *req, int32_t channels)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    if (channels < 1 || channels > 4) return fail(AAI_ERR_BAD_ARGUMENT, "Channels must be 1..4.");
-    aai::Geometry g;
-    {
-        std::string msg;
-        rc = aai::make_geometry(*req, g, msg);
-        if (rc != AAI_OK) return fail(rc, msg);
-    }
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    PlanRef p;
-    // (the plan of a packed fp32 image: what the device entries build on their first call)
-    rc = acquire_plan(*req, -1, -1, channels, rot_form(*req, g, channels, aai::SRC_F32, (int64_t)g.W * channels), &p);
-    if (rc == AAI_OK) g_lastError.clear();
-    return rc;
-}
-
-int aai_plan_info(const aai_request *req, int32_t channels, char *text, int32_t capacity)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    if (!text || capacity <= 0) return fail(AAI_ERR_BAD_ARGUMENT, "Null text buffer.");
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    const std::string d = plan_description(*req, channels);
-    snprintf(text, (size_t)capacity, "%s", d.c_str());
-    g_lastError.clear();
-    return AAI_OK;
-}
-
-int aai_shutdown(void)
-{
-    drop_plans();
-    g_lastError.clear();
-    return AAI_OK;
-}
-
-int aai_adjoint_batch_device_f32(const aai_request *req, int32_t batch,
-                                 const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
-                                 float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
-{
-    // argument errors are reported before the device is touched
-    aai::Geometry g;
-    int rc = check_adjoint(req, batch, d_gdst, dst_stride, d_gsrc, src_stride, g);
-    if (rc != AAI_OK) return rc;
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    rc = enqueue_adjoint(*req, g, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream);
-    if (rc == AAI_OK) g_lastError.clear();
-    return rc;
-}
-
-int aai_adjoint_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
-{
-    aai::Geometry g;
-    int rc = check_adjoint(req, 1, gdst, dst_stride, gsrc, src_stride, g);
-    if (rc != AAI_OK) return rc;
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    float *dGdst = nullptr, *dGsrc = nullptr;
-    hipStream_t stream = nullptr;
-    auto cleanup = [&]() {
-        if (dGdst) (void)hipFree(dGdst);
-        if (dGsrc) (void)hipFree(dGsrc);
-    };
-#define AAI_HIP_C(call)                                                        \
-    do {                                                                       \
-        hipError_t e__ = (call);                                               \
-        if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #call); }     \
-    } while (0)
-    AAI_HIP_C(hipMalloc((void **)&dGdst, sizeof(float) * (size_t)g.dW * g.dH));
-    AAI_HIP_C(hipMalloc((void **)&dGsrc, sizeof(float) * (size_t)g.W * g.H));
-    AAI_HIP_C(hipMemcpy2D(dGdst, sizeof(float) * g.dW, gdst, sizeof(float) * dst_stride, sizeof(float) * g.dW, g.dH, hipMemcpyHostToDevice));
-    rc = enqueue_adjoint(*req, g, 1, dGdst, g.dW, 0, dGsrc, g.W, 0, stream);
-    if (rc != AAI_OK) { cleanup(); return rc; }
-    AAI_HIP_C(hipStreamSynchronize(stream));
-    AAI_HIP_C(hipMemcpy2D(gsrc, sizeof(float) * src_stride, dGsrc, sizeof(float) * g.W, sizeof(float) * g.W, g.H, hipMemcpyDeviceToHost));
-    cleanup();
-#undef AAI_HIP_C
-    if (layout) fill_layout(g, resolved_kernel(*req, g), layout);
-    g_lastError.clear();
-    return AAI_OK;
-}
-
-int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)
-{
-    if (!d_dst || width < 0 || height < 0 || row0 < 0 || row1 < row0 || row1 > height || stride < width)
-        return fail(AAI_ERR_BAD_ARGUMENT, "Bad synthetic image arguments.");
-    int rc = require_device();
-    if (rc != AAI_OK) return rc;
-    AAI_HIP(aai::launch_synth_rows(d_dst, width, height, row0, row1, stride, seed, (hipStream_t)stream));
-    return AAI_OK;
-}
-
-int aai_synth_device_f32(float *d_dst, int32_t width, int32_t height, int64_t stride, uint64_t seed, void *stream)
-{
-    if (!d_dst || width < 0 || height < 0 || stride < width) return fail(AAI_ERR_BAD_ARGUMENT, "Bad synthetic image arguments.");
-    int rc = require_device();
-    if (rc != AAI_OK) return rc;
-    AAI_HIP(aai::launch_synth(d_dst, width, height, stride, seed, (hipStream_t)stream));
-    return AAI_OK;
-}
-
-int aai_resample_host(const aai_request *req, const void *src, int32_t src_dtype, int64_t src_stride,
-                      float *dst, int64_t dst_stride, aai_layout *layout)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    const size_t esz = src_dtype == AAI_DTYPE_F32 ? 4 : src_dtype == AAI_DTYPE_U8 ? 1 : src_dtype == AAI_DTYPE_U16 ? 2 : 0;
-    if (!esz) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown source element type.");
-    aai::Geometry g;
-    std::string msg;
-    rc = aai::make_geometry(*req, g, msg);
-    if (rc != AAI_OK) return fail(rc, msg);
-    if (!src || !dst) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
-    if (src_stride < g.W) return fail(AAI_ERR_BAD_ARGUMENT, "Source stride smaller than the image width.");
-    if (dst_stride < g.dW) return fail(AAI_ERR_BAD_ARGUMENT, "Destination stride smaller than the output width.");
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    void *dSrc = nullptr;
-    float *dDst = nullptr;
-    const size_t nDst = (size_t)g.dW * g.dH;
-    auto cleanup = [&]() { if (dSrc) (void)hipFree(dSrc); if (dDst) (void)hipFree(dDst); };
-#define AAI_HIP_C(call)                                                        \
-    do {                                                                       \
-        hipError_t e__ = (call);                                               \
-        if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #call); }     \
-    } while (0)
-    AAI_HIP_C(hipMalloc(&dSrc, esz * (size_t)g.W * g.H));      // no padding: every kernel clamps its vector loads into the image
-    AAI_HIP_C(hipMemcpy2D(dSrc, esz * g.W, src, esz * src_stride, esz * g.W, g.H, hipMemcpyHostToDevice));
-    if (nDst) {
-        AAI_HIP_C(hipMalloc((void **)&dDst, sizeof(float) * nDst));
-        rc = enqueue(*req, 1, dSrc, src_dtype, g.W, 0, dDst, g.dW, 0, nullptr);
-        if (rc != AAI_OK) { cleanup(); return rc; }
-        AAI_HIP_C(hipStreamSynchronize(nullptr));
-        AAI_HIP_C(hipMemcpy2D(dst, sizeof(float) * dst_stride, dDst, sizeof(float) * g.dW, sizeof(float) * g.dW, g.dH, hipMemcpyDeviceToHost));
-    }
-    cleanup();
-#undef AAI_HIP_C
-    if (layout) fill_layout(g, resolved_kernel(*req, g), layout);
-    g_lastError.clear();
-    return AAI_OK;
-}
-
-int aai_resample_interleaved_device(const aai_request *req, int32_t batch, int32_t channels,
-                                    const void *d_src, int32_t src_dtype, int64_t src_stride, int64_t src_image_stride,
-                                    float *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    if (channels < 1 || channels > 4) return fail(AAI_ERR_BAD_ARGUMENT, "Channels must be 1..4.");
-    if (batch < 0) return fail(AAI_ERR_BAD_ARGUMENT, "Negative batch.");
-    if (src_dtype != AAI_DTYPE_F32 && src_dtype != AAI_DTYPE_U8 && src_dtype != AAI_DTYPE_U16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown source element type.");
-    aai::Geometry g;
-    std::string msg;
-    rc = aai::make_geometry(*req, g, msg);
-    if (rc != AAI_OK) return fail(rc, msg);
-    if ((int64_t)g.W * channels > INT32_MAX / 2 || (int64_t)g.dW * channels > INT32_MAX / 2) return fail(AAI_ERR_TOO_LARGE, "Image too large.");
-    if (batch > 0 && g.dW > 0 && g.dH > 0 && (!d_src || !d_dst)) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    rc = enqueue(*req, batch, d_src, src_dtype, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream, -1, -1, channels);
-    if (rc == AAI_OK) g_lastError.clear();
-    return rc;
-}
-
-int aai_resample_interleaved_host(const aai_request *req, int32_t channels, const void *src, int32_t src_dtype, int64_t src_stride,
-                                  float *dst, int64_t dst_stride, aai_layout *layout)
-{
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    if (channels < 1 || channels > 4) return fail(AAI_ERR_BAD_ARGUMENT, "Channels must be 1..4.");
-    const size_t esz = src_dtype == AAI_DTYPE_F32 ? 4 : src_dtype == AAI_DTYPE_U8 ? 1 : src_dtype == AAI_DTYPE_U16 ? 2 : 0;
-    if (!esz) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown source element type.");
-    aai::Geometry g;
-    std::string msg;
-    rc = aai::make_geometry(*req, g, msg);
-    if (rc != AAI_OK) return fail(rc, msg);
-    if (!src || !dst) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
-    const int64_t rowIn = (int64_t)g.W * channels, rowOut = (int64_t)g.dW * channels;      // elements per dense row
-    if (rowIn > INT32_MAX / 2 || rowOut > INT32_MAX / 2) return fail(AAI_ERR_TOO_LARGE, "Image too large.");
-    if (src_stride < rowIn) return fail(AAI_ERR_BAD_ARGUMENT, "Source stride smaller than the image width.");
-    if (dst_stride < rowOut) return fail(AAI_ERR_BAD_ARGUMENT, "Destination stride smaller than the output width.");
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
-    void *dSrc = nullptr;
-    float *dDst = nullptr;
-    const size_t nDst = (size_t)rowOut * g.dH;
-    auto cleanup = [&]() { if (dSrc) (void)hipFree(dSrc); if (dDst) (void)hipFree(dDst); };
-#define AAI_HIP_C(call)                                                        \
-    do {                                                                       \
-        hipError_t e__ = (call);                                               \
-        if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #call); }     \
-    } while (0)
-    AAI_HIP_C(hipMalloc(&dSrc, esz * (size_t)rowIn * g.H));
-    AAI_HIP_C(hipMemcpy2D(dSrc, esz * rowIn, src, esz * src_stride, esz * rowIn, g.H, hipMemcpyHostToDevice));
-    if (nDst) {
-        AAI_HIP_C(hipMalloc((void **)&dDst, sizeof(float) * nDst));
-        rc = enqueue(*req, 1, dSrc, src_dtype, rowIn, 0, dDst, rowOut, 0, nullptr, -1, -1, channels);
-        if (rc != AAI_OK) { cleanup(); return rc; }
-        AAI_HIP_C(hipStreamSynchronize(nullptr));
-        AAI_HIP_C(hipMemcpy2D(dst, sizeof(float) * dst_stride, dDst, sizeof(float) * rowOut, sizeof(float) * rowOut, g.dH, hipMemcpyDeviceToHost));
-    }
-    cleanup();
-#undef AAI_HIP_C
-    if (layout) fill_layout(g, resolved_kernel(*req, g), layout);
-    g_lastError.clear();
-    return AAI_OK;
-}
-
-int aai_host_alloc(void **ptr, uint64_t bytes)
-{
-    if (!ptr) return fail(AAI_ERR_BAD_ARGUMENT, "Null pointer.");
-    int rc = require_device();
-    if (rc != AAI_OK) return rc;
-    AAI_HIP(hipHostMalloc(ptr, bytes ? (size_t)bytes : 1, hipHostMallocDefault));
-    g_lastError.clear();
-    return AAI_OK;
-}
-
-int aai_host_free(void *ptr)
-{
-    if (!ptr) return AAI_OK;
-    AAI_HIP(hipHostFree(ptr));
-    return AAI_OK;
-}
-
-namespace {
 
 // Device slots of the pipelined host-batch entry, kept between calls (allocating and freeing ~100 MB buffers costs
 // about as much as moving one 8-bit image over PCIe).  One pool per process; calls are serialised on its mutex.
@@ -541,63 +230,328 @@ bool is_page_locked(const void *p)
 
 }  // namespace
 
+extern "C" {
+
+int aai_version(void) { return AAI_VERSION_MAJOR * 1000 + AAI_VERSION_MINOR; }
+
+const char *aai_last_error(void) { return g_lastError.c_str(); }
+
+const char *aai_last_kernel(void) { return g_lastKernel.c_str(); }
+
+const char *aai_error_string(int code)
+{
+    switch (code) {
+    case AAI_OK: return "";
+    case AAI_ERR_RESOLUTION_MISMATCH: return "Assumed X & Y resolution are same.";
+    case AAI_ERR_RESOLUTION_NONPOSITIVE: return "0 or negative resolution is not acceptable.";
+    case AAI_ERR_NO_ROWS: return "There is no data in src array.";
+    case AAI_ERR_NO_COLUMNS: return "There is no data in the second dimension of src array.";
+    case AAI_ERR_NONFINITE: return "Non-finite argument.";
+    case AAI_ERR_BAD_ARGUMENT: return "Bad argument.";
+    case AAI_ERR_TOO_LARGE: return "Image too large.";
+    case AAI_ERR_NO_DEVICE: return "No HIP device available.";
+    case AAI_ERR_HIP: return "HIP runtime error.";
+    case AAI_ERR_EMPTY_OUTPUT: return "Output image would be empty.";
+    default: return "Unknown error.";
+    }
+}
+
+int aai_query(const aai_request *req, aai_layout *out)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    if (!out) return fail(AAI_ERR_BAD_ARGUMENT, "Null layout.");
+    AAI_TRY(request_geometry(*req, g));
+    return finish(*req, g, out);
+}
+
+int aai_device_count(int *count)
+{
+    if (!count) return fail(AAI_ERR_BAD_ARGUMENT, "Null count.");
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess) { (void)hipGetLastError(); n = 0; }
+    *count = n;
+    return AAI_OK;
+}
+
+int aai_set_device(int ordinal)
+{
+    AAI_TRY(require_device());
+    AAI_HIP(hipSetDevice(ordinal));
+    return AAI_OK;
+}
+
+int aai_device_synchronize(void)
+{
+    AAI_TRY(require_device());
+    AAI_HIP(hipDeviceSynchronize());
+    return AAI_OK;
+}
+
+int aai_resample_batch_device(const aai_request *req, int32_t batch, const void *d_src, int32_t src_dtype,
+                              int64_t src_stride, int64_t src_image_stride,
+                              float *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_dtype(src_dtype));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_pointers(d_src, d_dst));
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue(*req, g, batch, d_src, src_dtype, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_resample_batch_device_f32(const aai_request *req, int32_t batch,
+                                  const float *d_src, int64_t src_stride, int64_t src_image_stride,
+                                  float *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
+{
+    return aai_resample_batch_device(req, batch, d_src, AAI_DTYPE_F32, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, stream);
+}
+
+int aai_resample_batch_multi_device_f32(const aai_request *req, int32_t n_shards, const int32_t *devices, const int32_t *counts,
+                                        const float *const *d_src, int64_t src_stride, int64_t src_image_stride,
+                                        float *const *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *const *streams)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    if (n_shards < 0 || (n_shards > 0 && (!devices || !counts || !d_src || !d_dst))) return fail(AAI_ERR_BAD_ARGUMENT, "Bad shard description.");
+    AAI_TRY(request_geometry(*req, g));
+    for (int i = 0; i < n_shards; ++i) {
+        AAI_TRY(check_batch(counts[i]));
+        if (counts[i] > 0) AAI_TRY(check_pointers(d_src[i], d_dst[i]));
+    }
+    AAI_TRY(require_device());
+    int home = 0, rc = AAI_OK;
+    AAI_HIP(hipGetDevice(&home));
+    for (int i = 0; i < n_shards && rc == AAI_OK; ++i) {
+        if (counts[i] == 0) continue;
+        const hipError_t e = hipSetDevice(devices[i]);
+        if (e != hipSuccess) { rc = hip_fail(e, "hipSetDevice"); break; }
+        rc = enqueue(*req, g, counts[i], d_src[i], aai::SRC_F32, src_stride, src_image_stride, d_dst[i], dst_stride, dst_image_stride,
+                     streams ? (hipStream_t)streams[i] : nullptr);
+    }
+    (void)hipSetDevice(home);
+    if (rc == AAI_OK) g_lastError.clear();
+    return rc;
+}
+
+int aai_resample_device_f32(const aai_request *req, const float *d_src, int64_t src_stride,
+                            float *d_dst, int64_t dst_stride, void *stream)
+{
+    return aai_resample_batch_device_f32(req, 1, d_src, src_stride, 0, d_dst, dst_stride, 0, stream);
+}
+
+int aai_band_source_rows(const aai_request *req, int32_t dst_row0, int32_t dst_row1, int32_t *src_row0, int32_t *src_row1)
+{
+    aai::Geometry g;
+    return band_source_rows(req, dst_row0, dst_row1, src_row0, src_row1, g);
+}
+
+int aai_resample_band_device_f32(const aai_request *req, int32_t dst_row0, int32_t dst_row1,
+                                 const float *d_src_rows, int64_t src_stride, float *d_dst_rows, int64_t dst_stride, void *stream)
+{
+    aai::Geometry g;
+    int32_t a, b;
+    AAI_TRY(band_source_rows(req, dst_row0, dst_row1, &a, &b, g));
+    AAI_TRY(check_pointers(d_src_rows, d_dst_rows));
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue(*req, g, 1, d_src_rows, aai::SRC_F32, src_stride, 0, d_dst_rows, dst_stride, 0, (hipStream_t)stream, dst_row0, dst_row1));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_prepare(const aai_request *req, int32_t channels)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(require_device());
+    PlanRef p;
+    // (the plan of a packed fp32 image: what the device entries build on their first call)
+    AAI_TRY(acquire_plan(*req, g, -1, -1, channels, rot_form(*req, g, channels, aai::SRC_F32, (int64_t)g.W * channels), &p));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_plan_info(const aai_request *req, int32_t channels, char *text, int32_t capacity)
+{
+    AAI_TRY(check_request(req));
+    if (!text || capacity <= 0) return fail(AAI_ERR_BAD_ARGUMENT, "Null text buffer.");
+    AAI_TRY(require_device());
+    const std::string d = plan_description(*req, channels);
+    snprintf(text, (size_t)capacity, "%s", d.c_str());
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_shutdown(void)
+{
+    drop_plans();
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_adjoint_batch_device_f32(const aai_request *req, int32_t batch,
+                                 const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                 float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint(req, batch, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue_adjoint(*req, g, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_adjoint_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint(req, 1, gdst, dst_stride, gsrc, src_stride, g));
+    AAI_TRY(require_device());
+    DeviceBuffer dGdst, dGsrc;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dGdst.alloc(sizeof(float) * (size_t)g.dW * g.dH));
+    AAI_HIP(dGsrc.alloc(sizeof(float) * (size_t)g.W * g.H));
+    AAI_HIP(upload(dGdst, gdst, dst_stride, g.dW, g.dH, sizeof(float)));
+    AAI_TRY(enqueue_adjoint(*req, g, 1, dGdst.as<const float>(), g.dW, 0, dGsrc.as<float>(), g.W, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    AAI_HIP(download(gsrc, src_stride, dGsrc, g.W, g.H, sizeof(float)));
+    return finish(*req, g, layout);
+}
+
+int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)
+{
+    if (!d_dst || width < 0 || height < 0 || row0 < 0 || row1 < row0 || row1 > height || stride < width)
+        return fail(AAI_ERR_BAD_ARGUMENT, "Bad synthetic image arguments.");
+    AAI_TRY(require_device());
+    AAI_HIP(aai::launch_synth_rows(d_dst, width, height, row0, row1, stride, seed, (hipStream_t)stream));
+    return AAI_OK;
+}
+
+int aai_synth_device_f32(float *d_dst, int32_t width, int32_t height, int64_t stride, uint64_t seed, void *stream)
+{
+    if (!d_dst || width < 0 || height < 0 || stride < width) return fail(AAI_ERR_BAD_ARGUMENT, "Bad synthetic image arguments.");
+    AAI_TRY(require_device());
+    AAI_HIP(aai::launch_synth(d_dst, width, height, stride, seed, (hipStream_t)stream));
+    return AAI_OK;
+}
+
+int aai_resample_host(const aai_request *req, const void *src, int32_t src_dtype, int64_t src_stride,
+                      float *dst, int64_t dst_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_dtype(src_dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_pointers(src, dst));
+    AAI_TRY(check_strides(g, 1, src_stride, dst_stride));
+    AAI_TRY(require_device());
+    return host_round_trip(*req, g, 1, src_dtype, false, src, src_stride, dst, dst_stride, layout);
+}
+
+int aai_resample_interleaved_device(const aai_request *req, int32_t batch, int32_t channels,
+                                    const void *d_src, int32_t src_dtype, int64_t src_stride, int64_t src_image_stride,
+                                    float *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(check_dtype(src_dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_row_length(g, channels));
+    if (batch > 0 && g.dW > 0 && g.dH > 0) AAI_TRY(check_pointers(d_src, d_dst));
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue(*req, g, batch, d_src, src_dtype, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream, -1, -1, channels));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_resample_interleaved_host(const aai_request *req, int32_t channels, const void *src, int32_t src_dtype, int64_t src_stride,
+                                  float *dst, int64_t dst_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(check_dtype(src_dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_pointers(src, dst));
+    AAI_TRY(check_row_length(g, channels));
+    AAI_TRY(check_strides(g, channels, src_stride, dst_stride));
+    AAI_TRY(require_device());
+    return host_round_trip(*req, g, channels, src_dtype, false, src, src_stride, dst, dst_stride, layout);
+}
+
+int aai_host_alloc(void **ptr, uint64_t bytes)
+{
+    if (!ptr) return fail(AAI_ERR_BAD_ARGUMENT, "Null pointer.");
+    AAI_TRY(require_device());
+    AAI_HIP(hipHostMalloc(ptr, bytes ? (size_t)bytes : 1, hipHostMallocDefault));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_host_free(void *ptr)
+{
+    if (!ptr) return AAI_OK;
+    AAI_HIP(hipHostFree(ptr));
+    return AAI_OK;
+}
+
 int aai_resample_batch_host(const aai_request *req, int32_t batch, const void *src, int32_t src_dtype,
                             int64_t src_stride, int64_t src_image_stride,
                             float *dst, int64_t dst_stride, int64_t dst_image_stride, aai_layout *layout)
 {
-    int rc = check_request(req);
-    if (rc != AAI_OK) return rc;
-    const size_t esz = src_dtype == AAI_DTYPE_F32 ? 4 : src_dtype == AAI_DTYPE_U8 ? 1 : src_dtype == AAI_DTYPE_U16 ? 2 : 0;
-    if (!esz) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown source element type.");
-    if (batch < 0) return fail(AAI_ERR_BAD_ARGUMENT, "Negative batch.");
     aai::Geometry g;
-    std::string msg;
-    rc = aai::make_geometry(*req, g, msg);
-    if (rc != AAI_OK) return fail(rc, msg);
-    if (batch > 0 && (!src || !dst)) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
-    if (src_stride < g.W) return fail(AAI_ERR_BAD_ARGUMENT, "Source stride smaller than the image width.");
-    if (dst_stride < g.dW) return fail(AAI_ERR_BAD_ARGUMENT, "Destination stride smaller than the output width.");
-    rc = require_device();
-    if (rc != AAI_OK) return rc;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_dtype(src_dtype));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(request_geometry(*req, g));
+    if (batch > 0) AAI_TRY(check_pointers(src, dst));
+    AAI_TRY(check_strides(g, 1, src_stride, dst_stride));
+    AAI_TRY(require_device());
 
+    const size_t esz = aai::src_elem_size(src_dtype), srcRow = esz * g.W, dstRow = sizeof(float) * g.dW;      // bytes per dense row
     const size_t nDst = (size_t)g.dW * g.dH;
     if (batch > 0 && nDst) {
         std::lock_guard<std::mutex> lock(g_slotMutex);
         SlotPool &p = g_slots;
-        AAI_HIP(p.reserve(esz * (size_t)g.W * g.H, sizeof(float) * nDst));
+        AAI_HIP(p.reserve(srcRow * g.H, sizeof(float) * nDst));
         // Pageable buffers: the runtime's blocking copy (pinned bounce buffers, double-buffered) is its fastest path
         // and the asynchronous one much slower, so only page-locked buffers are copied asynchronously.
         const bool asyncUp = is_page_locked(src), asyncDown = is_page_locked(dst);
+        // one image between the host and a slot (dense rows there).  Dense host images go as one linear copy: the 2-D path
+        // copies row by row and is several times slower.
+        auto copy_image = [](void *to, size_t toPitch, const void *from, size_t fromPitch, size_t rowBytes, size_t rows, hipMemcpyKind kind,
+                             bool async, hipStream_t st) -> hipError_t {
+            if (toPitch == rowBytes && fromPitch == rowBytes)
+                return async ? hipMemcpyAsync(to, from, rowBytes * rows, kind, st) : hipMemcpy(to, from, rowBytes * rows, kind);
+            return async ? hipMemcpy2DAsync(to, toPitch, from, fromPitch, rowBytes, rows, kind, st) : hipMemcpy2D(to, toPitch, from, fromPitch, rowBytes, rows, kind);
+        };
         const char *srcBytes = static_cast<const char *>(src);
         hipError_t e = hipSuccess;
+        int rc = AAI_OK;
         for (int b = 0; b < batch && e == hipSuccess; ++b) {
             const int s = b % kSlots;
             hipStream_t st = p.streams[s];
-            // stream order protects the slot: this upload waits for the download of image b - kSlots.  Dense images
-            // go as one linear copy (the 2-D path copies row by row and is several times slower).
+            // stream order protects the slot: this upload waits for the download of image b - kSlots
             const char *hSrc = srcBytes + esz * (size_t)b * src_image_stride;
             float *hDst = dst + (size_t)b * dst_image_stride;
             if (!asyncUp) e = hipStreamSynchronize(st);          // a blocking copy does not wait for the slot's stream
             if (e != hipSuccess) break;
-            if (src_stride == g.W) {
-                e = asyncUp ? hipMemcpyAsync(p.dSrc[s], hSrc, esz * (size_t)g.W * g.H, hipMemcpyHostToDevice, st)
-                            : hipMemcpy(p.dSrc[s], hSrc, esz * (size_t)g.W * g.H, hipMemcpyHostToDevice);
-            } else {
-                e = asyncUp ? hipMemcpy2DAsync(p.dSrc[s], esz * g.W, hSrc, esz * src_stride, esz * g.W, g.H, hipMemcpyHostToDevice, st)
-                            : hipMemcpy2D(p.dSrc[s], esz * g.W, hSrc, esz * src_stride, esz * g.W, g.H, hipMemcpyHostToDevice);
-            }
+            e = copy_image(p.dSrc[s], srcRow, hSrc, esz * src_stride, srcRow, g.H, hipMemcpyHostToDevice, asyncUp, st);
             if (e != hipSuccess) break;
-            rc = enqueue(*req, 1, p.dSrc[s], src_dtype, g.W, 0, p.dDst[s], g.dW, 0, st);
+            rc = enqueue(*req, g, 1, p.dSrc[s], src_dtype, g.W, 0, p.dDst[s], g.dW, 0, st);
             if (rc != AAI_OK) break;
             if (!asyncDown) e = hipStreamSynchronize(st);
             if (e != hipSuccess) break;
-            if (dst_stride == g.dW) {
-                e = asyncDown ? hipMemcpyAsync(hDst, p.dDst[s], sizeof(float) * nDst, hipMemcpyDeviceToHost, st)
-                              : hipMemcpy(hDst, p.dDst[s], sizeof(float) * nDst, hipMemcpyDeviceToHost);
-            } else {
-                e = asyncDown ? hipMemcpy2DAsync(hDst, sizeof(float) * dst_stride, p.dDst[s], sizeof(float) * g.dW, sizeof(float) * g.dW, g.dH, hipMemcpyDeviceToHost, st)
-                              : hipMemcpy2D(hDst, sizeof(float) * dst_stride, p.dDst[s], sizeof(float) * g.dW, sizeof(float) * g.dW, g.dH, hipMemcpyDeviceToHost);
-            }
+            e = copy_image(hDst, sizeof(float) * dst_stride, p.dDst[s], dstRow, dstRow, g.dH, hipMemcpyDeviceToHost, asyncDown, st);
         }
         for (int s = 0; s < kSlots; ++s) {
             const hipError_t e2 = hipStreamSynchronize(p.streams[s]);
@@ -606,19 +560,17 @@ int aai_resample_batch_host(const aai_request *req, int32_t batch, const void *s
         if (rc != AAI_OK) return rc;
         if (e != hipSuccess) return hip_fail(e, "aai_resample_batch_host");
     }
-    if (layout) fill_layout(g, resolved_kernel(*req, g), layout);
-    g_lastError.clear();
-    return AAI_OK;
+    return finish(*req, g, layout);
 }
 
 int aai_resample_f32(const aai_request *req, const float *src, int64_t src_stride, float *dst, int64_t dst_stride, aai_layout *layout)
 {
-    return resample_host<float>(req, src, src_stride, dst, dst_stride, layout);
+    return resample_host_plain(req, false, src, src_stride, dst, dst_stride, layout);
 }
 
 int aai_resample_f64(const aai_request *req, const double *src, int64_t src_stride, double *dst, int64_t dst_stride, aai_layout *layout)
 {
-    return resample_host<double>(req, src, src_stride, dst, dst_stride, layout);
+    return resample_host_plain(req, true, src, src_stride, dst, dst_stride, layout);
 }
 
 }  // extern "C"

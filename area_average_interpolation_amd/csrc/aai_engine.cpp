@@ -410,14 +410,10 @@ int rot_form(const aai_request &rq, const aai::Geometry &g, int channels, int sr
     return aai::cell_can_serve(r, srcType, aai::ImageView{srcStride, 0}) ? aai::ROT_FORM_CELL : aai::ROT_FORM_QUAD;
 }
 
-int acquire_plan(const aai_request &rq, int band0, int band1, int channels, int form, PlanRef *out, bool onCallerStream, hipStream_t stream)
+int acquire_plan(const aai_request &rq, const aai::Geometry &g, int band0, int band1, int channels, int form, PlanRef *out, bool onCallerStream, hipStream_t stream)
 {
     int dev = -1;
     AAI_HIP(hipGetDevice(&dev));
-    aai::Geometry g;
-    std::string msg;
-    int rc = aai::make_geometry(rq, g, msg);
-    if (rc != AAI_OK) return fail(rc, msg);
     const int kernel = pick_kernel(rq, g);
     if (kernel != AAI_KERNEL_ROTATED) form = aai::ROT_FORM_QUAD;
     if (kernel != AAI_KERNEL_AXIS && (band0 >= 0 || channels != 1)) {
@@ -509,26 +505,17 @@ constexpr int kMaxGridZ = 65535;
 // element offset into a typed source buffer
 static const void *src_at(const void *base, int srcType, int64_t elements)
 {
-    const int64_t esz = srcType == aai::SRC_U8 ? 1 : srcType == aai::SRC_U16 ? 2 : 4;
-    return static_cast<const char *>(base) + elements * esz;
+    return static_cast<const char *>(base) + elements * (int64_t)aai::src_elem_size(srcType);
 }
 
-int enqueue(const aai_request &rq, int batch, const void *dSrc, int srcType, int64_t srcStride, int64_t srcImageStride,
+int enqueue(const aai_request &rq, const aai::Geometry &g, int batch, const void *dSrc, int srcType, int64_t srcStride, int64_t srcImageStride,
             float *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream, int band0, int band1, int channels)
 {
     PlanRef p;
-    int rc;
-    {
-        aai::Geometry g0;
-        std::string msg;
-        rc = aai::make_geometry(rq, g0, msg);
-        if (rc != AAI_OK) return fail(rc, msg);
-        rc = acquire_plan(rq, band0, band1, channels, rot_form(rq, g0, channels, srcType, srcStride), &p, /*onCallerStream*/ true, stream);
-    }
+    const int rc = acquire_plan(rq, g, band0, band1, channels, rot_form(rq, g, channels, srcType, srcStride), &p, /*onCallerStream*/ true, stream);
     if (rc != AAI_OK) return rc;
     // launches only enqueue; the plan's side stream and fork / join events are shared by its callers, hence the plan's lock
     std::lock_guard<std::mutex> lock(p->launch);
-    const aai::Geometry &g = p->g;
     // strides are in elements; an interleaved pixel takes `channels` of them
     if (srcStride < (int64_t)g.W * channels) return fail(AAI_ERR_BAD_ARGUMENT, "Source stride smaller than the image width.");
     if (dstStride < (int64_t)g.dW * channels) return fail(AAI_ERR_BAD_ARGUMENT, "Destination stride smaller than the output width.");
@@ -562,7 +549,7 @@ int enqueue(const aai_request &rq, int batch, const void *dSrc, int srcType, int
         }
     } else {
         // (an axis-aligned geometry lands here when the separable model fails for most of its pixels: `dense`)
-        const aai::QuadMap qm = aai::make_quad_map(g, srcStride, r.srcRow0, channels, srcType == aai::SRC_U8 ? 1 : srcType == aai::SRC_U16 ? 2 : 4);
+        const aai::QuadMap qm = aai::make_quad_map(g, srcStride, r.srcRow0, channels, aai::src_elem_size(srcType));
         aai::RotFlags flags;
         flags.list = p->dList; flags.count = p->flaggedPixels; flags.dense = p->dense;
         flags.masks = p->dMasks; flags.tileFlags = p->dTileFlags; flags.tileFlagWords = p->tileFlagWords; flags.live = p->dLive; flags.form = p->form;
@@ -587,23 +574,6 @@ int enqueue(const aai_request &rq, int batch, const void *dSrc, int srcType, int
     }
     g_lastKernel = name;
     if (e != hipSuccess) return hip_fail(e, name);
-    return AAI_OK;
-}
-
-int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride, Geometry &g)
-{
-    int rc = check_request(rq);
-    if (rc != AAI_OK) return rc;
-    if (batch < 0) return fail(AAI_ERR_BAD_ARGUMENT, "Negative batch.");
-    std::string msg;
-    rc = aai::make_geometry(*rq, g, msg);
-    if (rc != AAI_OK) return fail(rc, msg);
-    if (rq->mode == AAI_MODE_BILINEAR) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BILINEAR: the area and fast modes only.");
-    if (rq->mode == AAI_MODE_BICUBIC) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BICUBIC: the area and fast modes only.");
-    if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the adjoint.");
-    if (!gdst || !gsrc) return fail(AAI_ERR_BAD_ARGUMENT, "Null image pointer.");
-    if (srcStride < g.W) return fail(AAI_ERR_BAD_ARGUMENT, "Source stride smaller than the image width.");
-    if (dstStride < g.dW) return fail(AAI_ERR_BAD_ARGUMENT, "Destination stride smaller than the output width.");
     return AAI_OK;
 }
 

@@ -117,20 +117,19 @@ int require_device();
 // uploads, the one-off scans, K1's launch-shape measurement -- on `stream` when the caller has one to give (onCallerStream; a
 // stream that is being captured into a graph is not used), else on the device pool's build stream).
 // form: aai::RotForm of a rotated request's launch (rot_form below); ignored by the other kernels
-int acquire_plan(const aai_request &rq, int band0, int band1, int channels, int form, PlanRef *out, bool onCallerStream = false, hipStream_t stream = nullptr);
+int acquire_plan(const aai_request &rq, const Geometry &g, int band0, int band1, int channels, int form, PlanRef *out, bool onCallerStream = false, hipStream_t stream = nullptr);
 // "kernel=K rows=R nt=N swap=0 tune=T flagged=F dense=D form=M build_ms=B" of the cached whole-image plan ("" when there is none)
 std::string plan_description(const aai_request &rq, int channels);
 // which fp32 formulation serves a launch of this request: the cell formulation takes plain images below 4 GiB in area mode
 int rot_form(const aai_request &rq, const Geometry &g, int channels, int srcType, int64_t srcStride);
 
-// Enqueues one batched launch (plus the fix-up pass where the plan has one) on `stream`.  Strides in elements.
-int enqueue(const aai_request &rq, int batch, const void *dSrc, int srcType, int64_t srcStride, int64_t srcImageStride,
+// Enqueues one batched launch (plus the fix-up pass where the plan has one) on `stream`.  g: the request's geometry (make_geometry,
+// which the caller ran to validate the request).  Strides in elements.
+int enqueue(const aai_request &rq, const Geometry &g, int batch, const void *dSrc, int srcType, int64_t srcStride, int64_t srcImageStride,
             float *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream, int band0 = -1, int band1 = -1,
             int channels = 1);
 
-// The adjoint of an area / fast request: argument checks that need no device (mode, policy, batch, geometry, pointers, strides) ...
-int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride, Geometry &g);
-// ... and the two launches on `stream`, with stream-ordered scratch from the device pool's memory pool (hipMallocFromPoolAsync /
+// The adjoint of an area / fast request (the caller has checked the arguments): the two launches on `stream`, with stream-ordered scratch from the device pool's memory pool (hipMallocFromPoolAsync /
 // hipFreeAsync on `stream`): no plan, nothing blocks.  Strides in elements.
 int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
                     float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);

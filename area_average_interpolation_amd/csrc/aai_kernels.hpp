@@ -20,6 +20,12 @@ struct ImageView {
     int64_t imageStride;
 };
 
+// Small facts the launchers and their *_can_* predicates share, each stated once (host code; no kernel calls these).
+// bytes per element of a source type
+constexpr size_t src_elem_size(int srcType) { return srcType == SRC_U8 ? 1 : srcType == SRC_U16 ? 2 : 4; }
+// LDS words one window slot takes with `chan` interleaved channels of elemSize bytes each (8-bit RGB(A): one word, like a plain image)
+constexpr int slot_words(size_t elemSize, int chan) { return elemSize == 4 ? chan : (elemSize == 2 ? (chan + 1) / 2 : 1); }
+
 // ---- K1: axis-aligned separable kernel ----------------------------------------------------------------
 struct AxisLaunch {
     const AxisEntry *laneTab;   // device, nA entries (ascending source x)
@@ -66,6 +72,11 @@ struct RotFlags {
 };
 enum RotForm { ROT_FORM_QUAD = 0, ROT_FORM_CELL = 1 };
 size_t rotated_flag_words(const RotLaunch &r);      // waves of the tiling = 64-bit words of the mask array
+// the source image spans 4 GiB and more: unsigned 32-bit byte offsets from its first element no longer reach every pixel
+inline bool spans_4gib(const RotLaunch &r, int srcType, ImageView sv)
+{
+    return (int64_t)r.H * sv.rowStride * (int64_t)src_elem_size(srcType) >= ((int64_t)1 << 32);
+}
 hipError_t launch_knife_scan(const RotLaunch &r, unsigned long long *laneMasks, unsigned *counter, hipStream_t stream);
 // the double-precision fix-up pass over a list of dst pixels (defined in aai_rotated_strict.hip);
 // pixelList == NULL: the whole image (grid as for the production pass, at most 65535 tile rows)

@@ -411,22 +411,31 @@ hipError_t launch_knife_scan(const RotLaunch &r, unsigned long long *laneMasks, 
     return hipSuccess;
 }
 
-// the fp32 quad kernels serve this launch (RotLaunch::quad; area mode: plain and interleaved images; fast mode: plain images)
-static bool quad_serves(const RotLaunch &r, int srcType, ImageView sv)
-{
-    return r.quad && (r.mode == AAI_MODE_AREA || (r.mode == AAI_MODE_FAST && r.chan == 1)) && quad_can_address(r, srcType, sv);
-}
+// Which kernel family serves a launch on the rotated lattice: decided here, once, for the dispatch (launch_rotated_band) and for where
+// the fix-up pass may run (launch_rotated_typed).  The order of the tests IS the precedence: the samplers by mode; then the cell
+// formulation where the plan's scan was the cell scan (RotFlags::form) and the launch is one it takes; then, for footprints wider than
+// one 8 x 8 window, the quad formulation split into parts (aai_rotated_wide.hip); then the fp32 quad kernels (RotLaunch::quad; area
+// mode: plain and interleaved images; fast mode: plain images); what is left goes to the double-precision kernels, area mode with
+// wide footprints as runs.  DESIGN.md section 2 is this table in prose.
+enum RotKernel { SAMPLE_BILINEAR, SAMPLE_BICUBIC, CELL, WIDE, QUAD, FP64_RUNS, FP64 };
+struct RotFamily {
+    RotKernel kernel;
+    bool skipsFlagged;      // given the plan's lane masks it leaves the flagged pixels alone: the fix-up pass may run BESIDE it
+    const char *name;       // what aai_last_kernel() reports
+};
 
-// ... or the cell formulation does: the plan's scan was the cell scan (RotFlags::form) and the launch is one it takes
-static bool cell_serves(const RotLaunch &r, int srcType, ImageView sv, const RotFlags &flags)
+static RotFamily rot_family(const RotLaunch &r, int srcType, ImageView sv, int form)
 {
-    return flags.form == ROT_FORM_CELL && cell_can_serve(r, srcType, sv);
-}
-
-// ... or, for footprints wider than one 8 x 8 window, the quad formulation split into parts (aai_rotated_wide.hip)
-static bool wide_serves(const RotLaunch &r, int srcType, ImageView sv)
-{
-    return wide_can_serve(r, srcType, sv);
+    if (r.mode == AAI_MODE_BILINEAR) return {SAMPLE_BILINEAR, false, "aai_sample_kernel<bilinear>"};
+    if (r.mode == AAI_MODE_BICUBIC) return {SAMPLE_BICUBIC, false, "aai_sample_kernel<bicubic>"};
+    const bool fast = r.mode == AAI_MODE_FAST, multi = r.chan > 1;
+    if (form == ROT_FORM_CELL && cell_can_serve(r, srcType, sv)) return {CELL, true, multi ? "aai_cell_multi_kernel<area, channels>" : "aai_cell_kernel<area>"};
+    if (wide_can_serve(r, srcType, sv)) return {WIDE, true, fast ? "aai_wide_fast_kernel" : "aai_wide_kernel<area>"};
+    if (r.quad && (r.mode == AAI_MODE_AREA || (fast && !multi)) && quad_can_address(r, srcType, sv))
+        return {QUAD, true, multi ? "aai_quad_multi_kernel<area, channels>" : (fast ? "aai_quad_fast_kernel" : "aai_quad_kernel<area>")};
+    if (r.mode == AAI_MODE_AREA && r.runs) return {FP64_RUNS, false, multi ? "aai_rotated_runs_kernel<area, channels>" : "aai_rotated_runs_kernel<area>"};
+    if (fast) return {FP64, false, multi ? "aai_rotated_kernel<fast, channels>" : "aai_rotated_kernel<fast>"};
+    return {FP64, false, multi ? "aai_rotated_kernel<area, channels>" : "aai_rotated_kernel<area>"};
 }
 
 // one launch of at most 65535 tile rows (16-row tiles; the bicubic sampler: 8-row tiles)
@@ -434,64 +443,42 @@ template <typename T>
 static hipError_t launch_rotated_band(const RotLaunch &r, const QuadMap &m, const T *src, int srcType, ImageView sv, float *dst, ImageView dv,
                                       int batch, const RotFlags &flags, hipStream_t stream, const char **kernelName)
 {
-    if (r.mode == AAI_MODE_BILINEAR || r.mode == AAI_MODE_BICUBIC) {
-        const int tileRows = 4 * (r.mode == AAI_MODE_BILINEAR ? SampleRows<AAI_MODE_BILINEAR>::value : SampleRows<AAI_MODE_BICUBIC>::value);
-        dim3 grid((r.dW + 63) / 64 + (r.chan > 1 ? 0 : 1), (r.dyEnd - r.dyBase + tileRows - 1) / tileRows, batch);    // (+1: rows shift their columns left to a 256-byte boundary)
-        if (r.mode == AAI_MODE_BILINEAR) {
-            if (kernelName) *kernelName = "aai_sample_kernel<bilinear>";
-            hipLaunchKernelGGL((aai_sample_kernel<AAI_MODE_BILINEAR, T>), grid, dim3(kBlock), 0, stream, r, src, sv, dst, dv, flags.live);
+    const RotFamily f = rot_family(r, srcType, sv, flags.form);
+    if (kernelName) *kernelName = f.name;
+    const dim3 grid((r.dW + 15) / 16, (r.dyEnd - r.dyBase + 15) / 16, batch);
+    // the samplers' tiles: 64 columns (+1: rows shift their columns left to a 256-byte boundary) x 4 waves of SampleRows rows
+    auto sample_grid = [&](int tileRows) { return dim3((r.dW + 63) / 64 + (r.chan > 1 ? 0 : 1), (r.dyEnd - r.dyBase + tileRows - 1) / tileRows, batch); };
+    const unsigned long long *skip = flags.count ? flags.masks : nullptr;         // the flagged pixels belong to the fix-up pass
+    const bool fast = r.mode == AAI_MODE_FAST, multi = r.chan > 1;
+    switch (f.kernel) {
+    case SAMPLE_BILINEAR:
+        hipLaunchKernelGGL((aai_sample_kernel<AAI_MODE_BILINEAR, T>), sample_grid(4 * SampleRows<AAI_MODE_BILINEAR>::value), dim3(kBlock), 0, stream, r, src, sv, dst, dv, flags.live);
+        break;
+    case SAMPLE_BICUBIC:
+        hipLaunchKernelGGL((aai_sample_kernel<AAI_MODE_BICUBIC, T>), sample_grid(4 * SampleRows<AAI_MODE_BICUBIC>::value), dim3(kBlock), 0, stream, r, src, sv, dst, dv, flags.live);
+        break;
+    // the cell formulation: one lane per cell of the dst grid, every (dst, src) pair evaluated once
+    case CELL: return launch_cell(r, m, src, srcType, sv, dst, dv, batch, skip, stream);
+    case WIDE: return launch_wide(r, m, src, srcType, sv, dst, dv, batch, skip, stream);
+    // the fp32 quad formulation (interleaved channels: areas once per pair, applied to every channel; fast mode: centres in the dst
+    // square, fp32 in the dst frame)
+    case QUAD: return launch_quad(r, m, src, srcType, sv, dst, dv, batch, skip, stream, multi ? nullptr : flags.live);
+    // double precision; interleaved channels: the same kernels with the areas shared between the channels.  (The launches stand in
+    // the order the compiler has always met them in: it is the order of the kernels in the unit's code object.)
+    case FP64_RUNS:
+    case FP64: {
+        const bool runs = f.kernel == FP64_RUNS;      // (area mode only)
+        if (multi) {
+            if (runs) hipLaunchKernelGGL((aai_rotated_runs_kernel<T, true>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv);
+            else if (fast) hipLaunchKernelGGL((aai_rotated_kernel<AAI_MODE_FAST, false, T, true>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv, nullptr, 0u);
+            else hipLaunchKernelGGL((aai_rotated_kernel<AAI_MODE_AREA, false, T, true>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv, nullptr, 0u);
         } else {
-            if (kernelName) *kernelName = "aai_sample_kernel<bicubic>";
-            hipLaunchKernelGGL((aai_sample_kernel<AAI_MODE_BICUBIC, T>), grid, dim3(kBlock), 0, stream, r, src, sv, dst, dv, flags.live);
+            if (fast) hipLaunchKernelGGL((aai_rotated_kernel<AAI_MODE_FAST, false, T>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv, nullptr, 0u);
+            else if (runs) hipLaunchKernelGGL((aai_rotated_runs_kernel<T, false>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv);
+            else hipLaunchKernelGGL((aai_rotated_kernel<AAI_MODE_AREA, false, T>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv, nullptr, 0u);
         }
-        return hipGetLastError();
+        break;
     }
-    dim3 grid((r.dW + 15) / 16, (r.dyEnd - r.dyBase + 15) / 16, batch);
-    const bool quad = quad_serves(r, srcType, sv);
-    if (cell_serves(r, srcType, sv, flags)) {
-        // the cell formulation: one lane per cell of the dst grid, every (dst, src) pair evaluated once
-        if (kernelName) *kernelName = r.chan > 1 ? "aai_cell_multi_kernel<area, channels>" : "aai_cell_kernel<area>";
-        return launch_cell(r, m, src, srcType, sv, dst, dv, batch, flags.count ? flags.masks : nullptr, stream);
-    }
-    if (wide_serves(r, srcType, sv)) {
-        if (kernelName) *kernelName = r.mode == AAI_MODE_FAST ? "aai_wide_fast_kernel" : "aai_wide_kernel<area>";
-        return launch_wide(r, m, src, srcType, sv, dst, dv, batch, flags.count ? flags.masks : nullptr, stream);
-    }
-    if (r.chan > 1 && quad) {
-        // interleaved channels through the fp32 quad formulation: areas once per pair, applied to every channel
-        if (kernelName) *kernelName = "aai_quad_multi_kernel<area, channels>";
-        return launch_quad(r, m, src, srcType, sv, dst, dv, batch, flags.count ? flags.masks : nullptr, stream);
-    } else if (r.chan > 1) {
-        // interleaved channels: the same kernels with the areas shared between the channels
-        if (r.mode == AAI_MODE_AREA && r.runs) {
-            if (kernelName) *kernelName = "aai_rotated_runs_kernel<area, channels>";
-            hipLaunchKernelGGL((aai_rotated_runs_kernel<T, true>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv);
-        } else if (r.mode == AAI_MODE_FAST) {
-            if (kernelName) *kernelName = "aai_rotated_kernel<fast, channels>";
-            hipLaunchKernelGGL((aai_rotated_kernel<AAI_MODE_FAST, false, T, true>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv, nullptr, 0u);
-        } else {
-            if (kernelName) *kernelName = "aai_rotated_kernel<area, channels>";
-            hipLaunchKernelGGL((aai_rotated_kernel<AAI_MODE_AREA, false, T, true>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv, nullptr, 0u);
-        }
-    } else if (r.mode == AAI_MODE_FAST && quad) {
-        // centres in the dst square, fp32 in the dst frame; flagged pixels belong to the fix-up pass as in area mode
-        if (kernelName) *kernelName = "aai_quad_fast_kernel";
-        return launch_quad(r, m, src, srcType, sv, dst, dv, batch, flags.count ? flags.masks : nullptr, stream, flags.live);
-    } else if (r.mode == AAI_MODE_FAST) {
-        if (kernelName) *kernelName = "aai_rotated_kernel<fast>";
-        hipLaunchKernelGGL((aai_rotated_kernel<AAI_MODE_FAST, false, T>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv, nullptr, 0u);
-    } else if (quad) {
-        // the fp32 quad formulation; the pixels flagged by the plan's scans are recomputed by the fix-up pass
-        if (kernelName) *kernelName = "aai_quad_kernel<area>";
-        return launch_quad(r, m, src, srcType, sv, dst, dv, batch, flags.count ? flags.masks : nullptr, stream, flags.live);
-    } else {
-        if (r.runs) {
-            if (kernelName) *kernelName = "aai_rotated_runs_kernel<area>";
-            hipLaunchKernelGGL((aai_rotated_runs_kernel<T, false>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv);
-        } else {
-            if (kernelName) *kernelName = "aai_rotated_kernel<area>";
-            hipLaunchKernelGGL((aai_rotated_kernel<AAI_MODE_AREA, false, T>), grid, dim3(kRotBlock), 0, stream, r, src, sv, dst, dv, nullptr, 0u);
-        }
     }
     return hipGetLastError();
 }
@@ -519,7 +506,7 @@ static hipError_t launch_rotated_typed(const RotLaunch &r, const QuadMap &m, con
     // pass on the same stream -- or, when the production kernel is the quad kernel and skips those pixels, beside it on
     // the plan's side stream: fork before, join after.
     const bool fixup = !sampler && flags.count != 0;
-    bool beside = fixup && flags.masks && flags.side && (quad_serves(r, srcType, sv) || cell_serves(r, srcType, sv, flags) || wide_serves(r, srcType, sv));
+    bool beside = fixup && flags.masks && flags.side && rot_family(r, srcType, sv, flags.form).skipsFlagged;
     if (beside) {
         // a caller's stream that is being captured into a graph must not pull the plan's shared side stream into the
         // capture (another thread may use it meanwhile): the fix-up pass then follows the production pass in-stream

@@ -497,9 +497,6 @@ hipError_t launch_cell_typed(const RotLaunch &r, const QuadMap &m, const T *src,
     }
 }
 
-// LDS words one window slot takes with `chan` interleaved channels of T (QuadSrcMulti)
-template <typename T> constexpr int cell_slot_words(int chan) { return sizeof(T) == 4 ? chan : (sizeof(T) == 2 ? (chan + 1) / 2 : 1); }
-
 template <typename T, int WIN, int WORDS>
 hipError_t launch_cell_multi_words(const RotLaunch &r, const QuadConsts<float> &q, const CellConsts<float> &z, const QuadMap &m, const T *src, ImageView sv,
                                    float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
@@ -539,7 +536,7 @@ template <typename T, int WIN>
 hipError_t launch_cell_multi_win(const RotLaunch &r, const QuadConsts<float> &q, const CellConsts<float> &z, const QuadMap &m, const T *src, ImageView sv,
                                  float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
 {
-    const int words = cell_slot_words<T>(r.chan);
+    const int words = slot_words(sizeof(T), r.chan);      // (QuadSrcMulti)
     if constexpr (sizeof(T) == 1) return launch_cell_multi_words<T, WIN, 1>(r, q, z, m, src, sv, dst, dv, batch, skipMasks, stream);
     else if constexpr (sizeof(T) == 2) {
         if (words == 1) return launch_cell_multi_words<T, WIN, 1>(r, q, z, m, src, sv, dst, dv, batch, skipMasks, stream);
@@ -576,57 +573,37 @@ hipError_t launch_cell_multi_typed(const RotLaunch &r, const QuadMap &m, const T
 // The Makefile therefore compiles this file once per AAI_CELL_PART: 1 = dispatch + scan kernels, 2 = fp32 sources, 3 = fp32 sources
 // with hiPrec (rotations within a few degrees of an axis), 4 = 8-bit, 5 = 16-bit sources; a process pays for the unit it uses.
 // (AAI_CELL_PART undefined = everything in one unit.)
-hipError_t launch_cell_f32(const RotLaunch &r, const QuadMap &m, const float *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream);
-hipError_t launch_cell_f32_hp(const RotLaunch &r, const QuadMap &m, const float *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream);
-hipError_t launch_cell_u8(const RotLaunch &r, const QuadMap &m, const unsigned char *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream);
-hipError_t launch_cell_u16(const RotLaunch &r, const QuadMap &m, const unsigned short *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream);
-
+#define AAI_CELL_ENTRY(name, T) \
+    hipError_t name(const RotLaunch &r, const QuadMap &m, const T *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
+AAI_CELL_ENTRY(launch_cell_f32, float);
+AAI_CELL_ENTRY(launch_cell_f32_hp, float);
+AAI_CELL_ENTRY(launch_cell_u8, unsigned char);
+AAI_CELL_ENTRY(launch_cell_u16, unsigned short);
+AAI_CELL_ENTRY(launch_cell_multi_f32, float);
+AAI_CELL_ENTRY(launch_cell_multi_u8, unsigned char);
+AAI_CELL_ENTRY(launch_cell_multi_u16, unsigned short);
 #if !defined(AAI_CELL_PART) || AAI_CELL_PART == 2
-hipError_t launch_cell_f32(const RotLaunch &r, const QuadMap &m, const float *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
-{
-    return launch_cell_typed<float, 0>(r, m, src, sv, dst, dv, batch, skipMasks, stream);
-}
+AAI_CELL_ENTRY(launch_cell_f32, float) { return launch_cell_typed<float, 0>(r, m, src, sv, dst, dv, batch, skipMasks, stream); }
 #endif
 #if !defined(AAI_CELL_PART) || AAI_CELL_PART == 3
-hipError_t launch_cell_f32_hp(const RotLaunch &r, const QuadMap &m, const float *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
-{
-    return launch_cell_typed<float, 1>(r, m, src, sv, dst, dv, batch, skipMasks, stream);
-}
+AAI_CELL_ENTRY(launch_cell_f32_hp, float) { return launch_cell_typed<float, 1>(r, m, src, sv, dst, dv, batch, skipMasks, stream); }
 #endif
 #if !defined(AAI_CELL_PART) || AAI_CELL_PART == 4
-hipError_t launch_cell_u8(const RotLaunch &r, const QuadMap &m, const unsigned char *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
-{
-    return launch_cell_typed<unsigned char, 2>(r, m, src, sv, dst, dv, batch, skipMasks, stream);
-}
+AAI_CELL_ENTRY(launch_cell_u8, unsigned char) { return launch_cell_typed<unsigned char, 2>(r, m, src, sv, dst, dv, batch, skipMasks, stream); }
 #endif
 #if !defined(AAI_CELL_PART) || AAI_CELL_PART == 5
-hipError_t launch_cell_u16(const RotLaunch &r, const QuadMap &m, const unsigned short *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
-{
-    return launch_cell_typed<unsigned short, 2>(r, m, src, sv, dst, dv, batch, skipMasks, stream);
-}
+AAI_CELL_ENTRY(launch_cell_u16, unsigned short) { return launch_cell_typed<unsigned short, 2>(r, m, src, sv, dst, dv, batch, skipMasks, stream); }
 #endif
-
-hipError_t launch_cell_multi_f32(const RotLaunch &r, const QuadMap &m, const float *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream);
-hipError_t launch_cell_multi_u8(const RotLaunch &r, const QuadMap &m, const unsigned char *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream);
-hipError_t launch_cell_multi_u16(const RotLaunch &r, const QuadMap &m, const unsigned short *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream);
 #if !defined(AAI_CELL_PART) || AAI_CELL_PART == 6
-hipError_t launch_cell_multi_f32(const RotLaunch &r, const QuadMap &m, const float *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
-{
-    return launch_cell_multi_typed<float>(r, m, src, sv, dst, dv, batch, skipMasks, stream);
-}
+AAI_CELL_ENTRY(launch_cell_multi_f32, float) { return launch_cell_multi_typed<float>(r, m, src, sv, dst, dv, batch, skipMasks, stream); }
 #endif
 #if !defined(AAI_CELL_PART) || AAI_CELL_PART == 7
-hipError_t launch_cell_multi_u8(const RotLaunch &r, const QuadMap &m, const unsigned char *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
-{
-    return launch_cell_multi_typed<unsigned char>(r, m, src, sv, dst, dv, batch, skipMasks, stream);
-}
+AAI_CELL_ENTRY(launch_cell_multi_u8, unsigned char) { return launch_cell_multi_typed<unsigned char>(r, m, src, sv, dst, dv, batch, skipMasks, stream); }
 #endif
 #if !defined(AAI_CELL_PART) || AAI_CELL_PART == 8
-hipError_t launch_cell_multi_u16(const RotLaunch &r, const QuadMap &m, const unsigned short *src, ImageView sv, float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
-{
-    return launch_cell_multi_typed<unsigned short>(r, m, src, sv, dst, dv, batch, skipMasks, stream);
-}
+AAI_CELL_ENTRY(launch_cell_multi_u16, unsigned short) { return launch_cell_multi_typed<unsigned short>(r, m, src, sv, dst, dv, batch, skipMasks, stream); }
 #endif
+#undef AAI_CELL_ENTRY
 
 #if !defined(AAI_CELL_PART) || AAI_CELL_PART == 1
 bool cell_can_serve(const RotLaunch &r, int srcType, ImageView sv)
@@ -638,7 +615,7 @@ bool cell_can_serve(const RotLaunch &r, int srcType, ImageView sv)
     // pixels at 5.9 : 1) takes 71 us on 60 cell waves and 36 us on 390 one-shot quad waves.
     // (AAI_POLICY_PREFER_CELL asks for the cell kernel all the same)
     if (!r.preferCell && (int64_t)((r.dW + 62) / 63) * ((r.dH + 7) / 8) < 1024) return false;      // (in waves of 63 columns x 8 rows, whatever the wave's shape)
-    const int64_t esz = srcType == SRC_U8 ? 1 : srcType == SRC_U16 ? 2 : 4;
+    const int64_t esz = (int64_t)src_elem_size(srcType);
     if (r.chan > 1) {
         // interleaved channels (aai_cell_multi_kernel, 64 x 1 wave): windows whose slots fit 64 KiB of LDS, below 4 GiB
         if (r.chan > kQuadMaxChan) return false;
@@ -647,12 +624,11 @@ bool cell_can_serve(const RotLaunch &r, int srcType, ImageView sv)
         // 8- / 16-bit pixels without replication stay on aai_quad_multi_kernel (RGB 8-bit: 0.49 ms there, 0.68 here -- one lane's window
         // of packed words is unpacked for four dst pixels' sums, and four channels' sums cross lanes and rows)
         if (esz != 4 && r.scale <= 1 && !r.preferCell) return false;
-        const int words = esz == 4 ? r.chan : (esz == 2 ? (r.chan + 1) / 2 : 1);
         const CellConsts<float> z = make_cell_consts<float>(r.side, r.c, r.s);
-        if (z.win > 6 || z.win * z.win * words > kCellMultiMaxKiB) return false;
-        return (int64_t)r.H * sv.rowStride * esz < ((int64_t)1 << 32);
+        if (z.win > 6 || z.win * z.win * slot_words((size_t)esz, r.chan) > kCellMultiMaxKiB) return false;
+        return !spans_4gib(r, srcType, sv);
     }
-    if ((int64_t)r.H * sv.rowStride * esz < ((int64_t)1 << 32)) return true;
+    if (!spans_4gib(r, srcType, sv)) return true;
     // 4 GiB and more: every wave rebases its offsets on its own first source row (aai_cell_kernel, QuadMap::rebaseWaves); the rows one
     // wave can touch -- 64 cell columns and up to 33 cell rows of `side` lattice points each, plus its windows -- must span less than
     // 4 GiB, and the 24-bit multiplies of the window addresses need a pitch below 8 MiB
@@ -666,10 +642,7 @@ hipError_t launch_cell(const RotLaunch &r, const QuadMap &map, const void *src, 
     if (r.dW <= 0 || r.dyEnd <= r.dyBase || batch <= 0) return hipSuccess;
     QuadMap m = map;
     m.anchorRows = 0;
-    {
-        const int64_t esz = srcType == SRC_U8 ? 1 : srcType == SRC_U16 ? 2 : 4;
-        m.rebaseWaves = (int64_t)r.H * sv.rowStride * esz >= ((int64_t)1 << 32) ? 1 : 0;
-    }
+    m.rebaseWaves = spans_4gib(r, srcType, sv) ? 1 : 0;
     if (r.chan > 1) {
         m.rebaseWaves = 0;
         switch (srcType) {

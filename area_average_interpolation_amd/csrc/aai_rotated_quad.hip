@@ -334,9 +334,6 @@ hipError_t launch_quad_win(const RotLaunch &r, const QuadConsts<float> &q, const
     return hipGetLastError();
 }
 
-// LDS words one window slot takes with `chan` interleaved channels of T
-template <typename T> int quad_slot_words(int chan) { return sizeof(T) == 4 ? chan : (sizeof(T) == 2 ? (chan + 1) / 2 : 1); }
-
 template <typename T, int WIN, int WORDS>
 hipError_t launch_quad_multi_words(const RotLaunch &r, const QuadConsts<float> &q, const QuadMap &m, const T *src, ImageView sv, float *dst, ImageView dv,
                                    int batch, const unsigned long long *skipMasks, hipStream_t stream)
@@ -365,7 +362,7 @@ hipError_t launch_quad_multi_win(const RotLaunch &r, const QuadConsts<float> &q,
                                  int batch, const unsigned long long *skipMasks, hipStream_t stream)
 {
     // quad_can_address() keeps WIN * WIN * words <= 80 KiB of LDS per block
-    const int words = quad_slot_words<T>(r.chan);
+    const int words = slot_words(sizeof(T), r.chan);
     if (sizeof(T) == 1) return launch_quad_multi_words<T, WIN, 1>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
     if (sizeof(T) == 2) {
         if (words == 1) return launch_quad_multi_words<T, WIN, 1>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
@@ -439,30 +436,29 @@ AAI_QUAD_ENTRY(launch_quad_u16, unsigned short) { return launch_quad_typed<unsig
 #undef AAI_QUAD_ENTRY
 
 #if !defined(AAI_QUAD_PART) || AAI_QUAD_PART == 1
+// the widest window of source pixels a dst pixel's footprint can touch, per axis
+static int quad_window(const RotLaunch &r) { return (int)floor(2.0 * (r.h * (r.c + r.s) - 0.5 + 1e-5)) + 3; }
+
 // How many source rows apart two lanes of one wave (a 16 x 4 dst tile) can read: their centres differ by at most
 // 15.6 dst pixel sides, each reaches half a window further, plus slack for rounding and clamping.
 int quad_anchor_rows(const RotLaunch &r)
 {
-    const int win = (int)floor(2.0 * (r.h * (r.c + r.s) - 0.5 + 1e-5)) + 3;
-    return (int)ceil(15.6 * 2.0 * r.h / r.scale) + win + 4;
+    return (int)ceil(15.6 * 2.0 * r.h / r.scale) + quad_window(r) + 4;
 }
 
 bool quad_can_address(const RotLaunch &r, int srcType, ImageView sv)
 {
     // lanes address their pixels with unsigned 32-bit byte offsets from the image's first element -- or, for plain images
     // of 4 GiB and more, from an anchor row of their wave (quad_anchor_rows)
-    const int64_t esz = srcType == SRC_U8 ? 1 : srcType == SRC_U16 ? 2 : 4;
-    if ((int64_t)r.H * sv.rowStride * esz >= ((int64_t)1 << 32)) {
+    const int win = quad_window(r);
+    if (spans_4gib(r, srcType, sv)) {
         if (r.chan > 1) return false;
-        const int win = (int)floor(2.0 * (r.h * (r.c + r.s) - 0.5 + 1e-5)) + 3;
-        if ((int64_t)(2 * quad_anchor_rows(r) + win + 2) * sv.rowStride * esz >= ((int64_t)1 << 32)) return false;
+        if ((int64_t)(2 * quad_anchor_rows(r) + win + 2) * sv.rowStride * (int64_t)src_elem_size(srcType) >= ((int64_t)1 << 32)) return false;
     }
     if (r.chan > 1) {
         // interleaved channels: the staged window (win^2 slots of `words` LDS words per lane) must leave room for two
         // workgroups per CU
-        const int win = (int)floor(2.0 * (r.h * (r.c + r.s) - 0.5 + 1e-5)) + 3;
-        const int words = esz == 4 ? r.chan : (esz == 2 ? (r.chan + 1) / 2 : 1);
-        if (win * win * words > 80) return false;
+        if (win * win * slot_words(src_elem_size(srcType), r.chan) > 80) return false;
     }
     return true;
 }
@@ -472,8 +468,7 @@ hipError_t launch_quad(const RotLaunch &r, const QuadMap &map, const void *src, 
 {
     if (r.dW <= 0 || r.dyEnd <= r.dyBase || batch <= 0) return hipSuccess;
     QuadMap m = map;
-    const int64_t esz = srcType == SRC_U8 ? 1 : srcType == SRC_U16 ? 2 : 4;
-    m.anchorRows = (int64_t)r.H * sv.rowStride * esz >= ((int64_t)1 << 32) ? quad_anchor_rows(r) : 0;
+    m.anchorRows = spans_4gib(r, srcType, sv) ? quad_anchor_rows(r) : 0;
     switch (srcType) {
     case SRC_U8: return launch_quad_u8(r, m, static_cast<const unsigned char *>(src), sv, dst, dv, batch, skipMasks, stream, live);
     case SRC_U16: return launch_quad_u16(r, m, static_cast<const unsigned short *>(src), sv, dst, dv, batch, skipMasks, stream, live);

@@ -284,8 +284,7 @@ hipError_t launch_wide(const RotLaunch &r, const QuadMap &map, const void *src, 
 {
     if (r.dW <= 0 || r.dyEnd <= r.dyBase || batch <= 0) return hipSuccess;
     QuadMap m = map;
-    const int64_t esz = srcType == SRC_U8 ? 1 : srcType == SRC_U16 ? 2 : 4;
-    m.anchorRows = (int64_t)r.H * sv.rowStride * esz >= ((int64_t)1 << 32) ? quad_anchor_rows(r) : 0;
+    m.anchorRows = spans_4gib(r, srcType, sv) ? quad_anchor_rows(r) : 0;
     switch (srcType) {
     case SRC_U8: return launch_wide_u8(r, m, static_cast<const unsigned char *>(src), sv, dst, dv, batch, skipMasks, stream);
     case SRC_U16: return launch_wide_u16(r, m, static_cast<const unsigned short *>(src), sv, dst, dv, batch, skipMasks, stream);

@@ -13,7 +13,10 @@
  * INTEGRATION.md shows the binding a maintainer of the reference would add.
  *
  * Conventions (all taken from the reference):
- *   - images are row-major [y][x] (Source.cpp:31, 150); strides are in ELEMENTS, not bytes;
+ *   - images are row-major [y][x] (Source.cpp:31, 150); strides are in ELEMENTS, not bytes, and only need to be >= width * channels:
+ *     the elements between the end of a row and the next row, and between the end of a batch image and the next image, are never
+ *     read (not even with weight 0: they may hold NaN bit patterns) and never written; nor is anything before the first or after
+ *     the last element of a buffer, whatever its alignment (tests/test_gpu_memory_contract.py holds every kernel to this);
  *   - `first` = x, `second` = y for every pair (Source.cpp:43-46);
  *   - resolutions in pixel/mm or dpi, only their ratio matters, x and y must agree (Source.cpp:112-117);
  *   - isocenter in pixel-centre coordinates of the input image (Source.cpp:82);
@@ -247,7 +250,8 @@ int aai_resample_batch_host(const aai_request *req, int32_t batch, const void *s
  * dst rows [dst_row0, dst_row1) only: for sharding ONE image over several GPUs (each rank computes a band, no
  * collective: a band only reads its own source footprint) or for images larger than device memory.
  * aai_band_source_rows (host only) tells which source rows [src_row0, src_row1) the band reads; the device call
- * takes d_src_rows = address of source row src_row0 (a buffer holding just those rows is enough) and
+ * takes d_src_rows = address of source row src_row0 (a buffer holding just those rows is enough: the rows before src_row0 and from
+ * src_row1 on are never read, and the padding of the rows in between is neither read nor written, like everywhere else) and
  * d_dst_rows = address of output row dst_row0.  For rotated requests dst_row0 must be a multiple of 16.  The band
  * results are bit-identical to the same rows of the full-image call. */
 int aai_band_source_rows(const aai_request *req, int32_t dst_row0, int32_t dst_row1, int32_t *src_row0, int32_t *src_row1);

@@ -89,6 +89,12 @@ SYMBOLS = {
     "aai_shutdown": (ctypes.c_int, []),
     "aai_last_kernel": (ctypes.c_char_p, []),
 }
+# the extension header include/aai_adjoint_planned.h (SYMBOLS mirrors include/aai.h, entry for entry)
+PLANNED_SYMBOLS = {
+    "aai_adjoint_prepare": (ctypes.c_int, [_RQ]),
+    "aai_adjoint_planned_batch_device_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_adjoint_planned_f32": (ctypes.c_int, [_RQ, _P, _I64, _P, _I64, _LY]),
+}
 
 _lib = None
 
@@ -110,7 +116,7 @@ def load():
             except ImportError:
                 pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

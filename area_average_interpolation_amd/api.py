@@ -278,20 +278,32 @@ def resample_device(request, src_ptr, src_stride, dst_ptr, dst_stride, stream=0,
 
 
 def adjoint_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None,
-                   dst_image_stride=0, src_image_stride=0):
+                   dst_image_stride=0, src_image_stride=0, planned=False):
     """aai_adjoint_batch_device_f32: gsrc = W(request)^T gdst on device-resident fp32 images -- the transpose of what
     resample_device computes (area and fast modes).  Raw device pointers (ints), strides in elements, a hipStream_t handle;
-    every element of the src_width x src_height gradient image is written."""
-    rc = L.load().aai_adjoint_batch_device_f32(_ref(request), 1 if batch is None else int(batch), gdst_ptr, dst_stride, dst_image_stride,
-                                               gsrc_ptr, src_stride, src_image_stride, stream)
+    every element of the src_width x src_height gradient image is written.
+    planned=True: aai_adjoint_planned_batch_device_f32 -- at rotations by multiples of 90 degrees the transposed separable kernel
+    on the forward's cached plan (fp32; the first call of a geometry builds the plan's adjoint tables and synchronises, see
+    adjoint_prepare), the same general kernels for every other request."""
+    fn = L.load().aai_adjoint_planned_batch_device_f32 if planned else L.load().aai_adjoint_batch_device_f32
+    rc = fn(_ref(request), 1 if batch is None else int(batch), gdst_ptr, dst_stride, dst_image_stride,
+            gsrc_ptr, src_stride, src_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def adjoint_prepare(request):
+    """aai_adjoint_prepare: aai_prepare plus the adjoint tables of the plan, so that adjoint_device(..., planned=True) only
+    enqueues.  A validated no-op for requests the planned adjoint hands to the general kernels."""
+    rc = L.load().aai_adjoint_prepare(_ref(request))
     if rc != L.OK:
         raise AaiError(rc, last_error())
 
 
 def adjoint_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle,
-                 mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
-    """Host-buffer adjoint (aai_adjoint_f32): gdst is the [dH, dW] gradient with respect to the output of
-    resample_host(src of shape src_shape = (H, W), ...); returns (code, message, gsrc [H, W] float32 or None)."""
+                 mode=L.MODE_AREA, policy=L.POLICY_REFERENCE, planned=False):
+    """Host-buffer adjoint (aai_adjoint_f32; planned=True: aai_adjoint_planned_f32): gdst is the [dH, dW] gradient with respect to
+    the output of resample_host(src of shape src_shape = (H, W), ...); returns (code, message, gsrc [H, W] float32 or None)."""
     lib = L.load()
     H, W = int(src_shape[0]), int(src_shape[1])
     rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
@@ -302,7 +314,8 @@ def adjoint_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter,
     if g.shape != (lay.dst_height, lay.dst_width):
         raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width),))
     gsrc = np.empty((H, W), dtype=np.float32)
-    rc = lib.aai_adjoint_f32(_ref(rq), g.ctypes.data, max(lay.dst_width, 1), gsrc.ctypes.data, W, None)
+    fn = lib.aai_adjoint_planned_f32 if planned else lib.aai_adjoint_f32
+    rc = fn(_ref(rq), g.ctypes.data, max(lay.dst_width, 1), gsrc.ctypes.data, W, None)
     if rc != L.OK:
         return rc, last_error(), None
     return rc, "", gsrc
@@ -342,7 +355,7 @@ def resample_band_device(request, dst_row0, dst_row1, src_rows_ptr, src_stride, 
 
 def plan_shape(request, channels=1):
     """aai_plan_info: one line describing the cached whole-image plan of this request on the current device ("" if none):
-    kernel family, K1 launch shape and its origin, flagged pixels, fp32 formulation, build time."""
+    kernel family, K1 launch shape and its origin, flagged pixels, fp32 formulation, build time, adjoint tables (tables | none)."""
     buf = ctypes.create_string_buffer(512)
     rc = L.load().aai_plan_info(_ref(request), int(channels), buf, 512)
     if rc != L.OK:

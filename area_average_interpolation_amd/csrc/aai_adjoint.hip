@@ -42,6 +42,45 @@ __global__ __launch_bounds__(kAdjTile *kAdjTile) void aai_adjoint_gather_kernel(
     gsrc[(int64_t)blockIdx.z * sv.imageStride + (int64_t)sy * sv.rowStride + sx] = (float)g;
 }
 
+// The two passes over lists of pixels: the per-pixel bodies of the whole-image kernels above, one lane per list entry (x, y).
+constexpr int kAdjListBlock = 256;
+
+template <int MODE>
+__global__ __launch_bounds__(kAdjListBlock) void aai_adjoint_norm_listed_kernel(RotLaunch r, const float *__restrict__ gdst, ImageView dv,
+                                                                                double *__restrict__ n, const uint2 *__restrict__ list, unsigned count)
+{
+    const unsigned i = blockIdx.x * kAdjListBlock + threadIdx.x;
+    if (i >= count) return;
+    const int dx = (int)list[i].x, dy = (int)list[i].y;
+    const float gd = gdst[(int64_t)blockIdx.z * dv.imageStride + (int64_t)dy * dv.rowStride + dx];
+    n[((int64_t)blockIdx.z * r.dH + dy) * r.dW + dx] = adjoint_normalised<MODE>(r, dx, dy, (double)gd);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kAdjListBlock) void aai_adjoint_gather_listed_kernel(RotLaunch r, const double *__restrict__ n, float *__restrict__ gsrc,
+                                                                                 ImageView sv, const uint2 *__restrict__ list, unsigned count)
+{
+    const unsigned i = blockIdx.x * kAdjListBlock + threadIdx.x;
+    if (i >= count) return;
+    const int sx = (int)list[i].x, sy = (int)list[i].y;
+    const double g = adjoint_gather<MODE>(r, sx, sy, n + (int64_t)blockIdx.z * r.dH * r.dW);
+    gsrc[(int64_t)blockIdx.z * sv.imageStride + (int64_t)sy * sv.rowStride + sx] = (float)g;
+}
+
+hipError_t launch_adjoint_listed(const RotLaunch &r, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
+                                 const uint2 *dstList, unsigned nDst, const uint2 *srcList, unsigned nSrc, hipStream_t stream)
+{
+    if (batch <= 0 || !nDst || !nSrc) return hipSuccess;
+    const dim3 block(kAdjListBlock, 1, 1), gridD((nDst + kAdjListBlock - 1) / kAdjListBlock, 1, batch), gridS((nSrc + kAdjListBlock - 1) / kAdjListBlock, 1, batch);
+    if (r.mode == AAI_MODE_FAST) hipLaunchKernelGGL(aai_adjoint_norm_listed_kernel<AAI_MODE_FAST>, gridD, block, 0, stream, r, gdst, dv, n, dstList, nDst);
+    else hipLaunchKernelGGL(aai_adjoint_norm_listed_kernel<AAI_MODE_AREA>, gridD, block, 0, stream, r, gdst, dv, n, dstList, nDst);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (r.mode == AAI_MODE_FAST) hipLaunchKernelGGL(aai_adjoint_gather_listed_kernel<AAI_MODE_FAST>, gridS, block, 0, stream, r, n, gsrc, sv, srcList, nSrc);
+    else hipLaunchKernelGGL(aai_adjoint_gather_listed_kernel<AAI_MODE_AREA>, gridS, block, 0, stream, r, n, gsrc, sv, srcList, nSrc);
+    return hipGetLastError();
+}
+
 // `batch` images (at most 65535: grid.z); n holds batch x dH x dW doubles.  Only enqueues.
 hipError_t launch_adjoint(const RotLaunch &r, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
                           hipStream_t stream, const char **kernelName)

@@ -100,6 +100,22 @@ AAI_HD void adjoint_virtual_pixel(const RotLaunch &r, int sx, int sy, int jx, in
     }
 }
 
+// the dst pixels [dxa, dxb] x [dya, dyb] whose window can hold virtual pixel (X, Y) (false: none); R = adjoint_reach(r), rL = 1 / side.
+// (Shared with the host, which lists the dst pixels a listed gather reads: aai_plan.cpp, build_adjoint_lists.)
+AAI_HD bool adjoint_candidates(const RotLaunch &r, int X, int Y, double R, double rL, int &dxa, int &dxb, int &dya, int &dyb)
+{
+    // (X, Y) in the dst lattice: the inverse of pixel_centre, px = cXa dx + cXb dy + cX0 with (cXa, cXb) = side (cs, sn),
+    // py = cYa dx + cYb dy + cY0 with (cYa, cYb) = side (-sn, cs)
+    const double u = X - r.cX0, v = Y - r.cY0;
+    const double fx = (u * r.cs - v * r.sn) * rL, fy = (u * r.sn + v * r.cs) * rL;
+    // clamp in double before converting
+    const double xa = fmax(ceil(fx - R), 0.0), xb = fmin(floor(fx + R), (double)(r.dW - 1));
+    const double ya = fmax(ceil(fy - R), 0.0), yb = fmin(floor(fy + R), (double)(r.dH - 1));
+    if (!(xa <= xb) || !(ya <= yb)) return false;
+    dxa = (int)xa; dxb = (int)xb; dya = (int)ya; dyb = (int)yb;
+    return true;
+}
+
 // pass 2: the gradient of source pixel (sx, sy); n = pass 1's image of this batch entry, dW elements per row
 template <int MODE>
 AAI_HD double adjoint_gather(const RotLaunch &r, int sx, int sy, const double *n)
@@ -110,15 +126,8 @@ AAI_HD double adjoint_gather(const RotLaunch &r, int sx, int sy, const double *n
         for (int jx = 0; jx < r.scale; ++jx) {
             int X, Y;
             adjoint_virtual_pixel(r, sx, sy, jx, jy, X, Y);
-            // (X, Y) in the dst lattice: the inverse of pixel_centre, px = cXa dx + cXb dy + cX0 with (cXa, cXb) = side (cs, sn),
-            // py = cYa dx + cYb dy + cY0 with (cYa, cYb) = side (-sn, cs)
-            const double u = X - r.cX0, v = Y - r.cY0;
-            const double fx = (u * r.cs - v * r.sn) * rL, fy = (u * r.sn + v * r.cs) * rL;
-            // clamp in double before converting
-            const double xa = fmax(ceil(fx - R), 0.0), xb = fmin(floor(fx + R), (double)(r.dW - 1));
-            const double ya = fmax(ceil(fy - R), 0.0), yb = fmin(floor(fy + R), (double)(r.dH - 1));
-            if (!(xa <= xb) || !(ya <= yb)) continue;
-            const int dxa = (int)xa, dxb = (int)xb, dya = (int)ya, dyb = (int)yb;
+            int dxa, dxb, dya, dyb;
+            if (!adjoint_candidates(r, X, Y, R, rL, dxa, dxb, dya, dyb)) continue;
             for (int dy = dya; dy <= dyb; ++dy)
                 for (int dx = dxa; dx <= dxb; ++dx) {
                     double px, py;

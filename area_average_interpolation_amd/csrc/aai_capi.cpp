@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "aai_engine.hpp"
+#include "../../include/aai_adjoint_planned.h"
 
 using namespace aai::engine;
 
@@ -78,8 +79,9 @@ int check_strides(const aai::Geometry &g, int channels, int64_t srcStride, int64
     return AAI_OK;
 }
 
-// The adjoint of an area / fast request: the argument checks of both entries, none of which needs a device
-int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride, aai::Geometry &g)
+// The adjoint of an area / fast request: the argument checks of every adjoint entry, none of which needs a device -- the request's
+// part (all aai_adjoint_prepare has to check) ...
+int check_adjoint_request(const aai_request *rq, int batch, aai::Geometry &g)
 {
     AAI_TRY(check_request(rq));
     AAI_TRY(check_batch(batch));
@@ -87,8 +89,29 @@ int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t ds
     if (rq->mode == AAI_MODE_BILINEAR) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BILINEAR: the area and fast modes only.");
     if (rq->mode == AAI_MODE_BICUBIC) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BICUBIC: the area and fast modes only.");
     if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the adjoint.");
+    return AAI_OK;
+}
+// ... and the images'
+int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride, aai::Geometry &g)
+{
+    AAI_TRY(check_adjoint_request(rq, batch, g));
     AAI_TRY(check_pointers(gdst, gsrc));
     return check_strides(g, 1, srcStride, dstStride);
+}
+
+typedef int (*AdjointEnqueue)(const aai_request &, const aai::Geometry &, int, const float *, int64_t, int64_t, float *, int64_t, int64_t, hipStream_t);
+
+// aai_adjoint_batch_device_f32 / aai_adjoint_planned_batch_device_f32
+int adjoint_device(AdjointEnqueue run, const aai_request *req, int32_t batch, const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                   float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint(req, batch, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(run(*req, g, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
 }
 
 int finish(const aai_request &rq, const aai::Geometry &g, aai_layout *layout)
@@ -226,6 +249,23 @@ bool is_page_locked(const void *p)
     hipPointerAttribute_t attr{};
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return attr.type == hipMemoryTypeHost;
+}
+
+// aai_adjoint_f32 / aai_adjoint_planned_f32: upload gdst, one launch on the null stream, download gsrc
+int adjoint_host(AdjointEnqueue run, const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint(req, 1, gdst, dst_stride, gsrc, src_stride, g));
+    AAI_TRY(require_device());
+    DeviceBuffer dGdst, dGsrc;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dGdst.alloc(sizeof(float) * (size_t)g.dW * g.dH));
+    AAI_HIP(dGsrc.alloc(sizeof(float) * (size_t)g.W * g.H));
+    AAI_HIP(upload(dGdst, gdst, dst_stride, g.dW, g.dH, sizeof(float)));
+    AAI_TRY(run(*req, g, 1, dGdst.as<const float>(), g.dW, 0, dGsrc.as<float>(), g.W, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    AAI_HIP(download(gsrc, src_stride, dGsrc, g.W, g.H, sizeof(float)));
+    return finish(*req, g, layout);
 }
 
 }  // namespace
@@ -400,29 +440,34 @@ int aai_adjoint_batch_device_f32(const aai_request *req, int32_t batch,
                                  const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
                                  float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
-    aai::Geometry g;
-    AAI_TRY(check_adjoint(req, batch, d_gdst, dst_stride, d_gsrc, src_stride, g));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue_adjoint(*req, g, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    return adjoint_device(enqueue_adjoint, req, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
 }
 
 int aai_adjoint_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
 {
+    return adjoint_host(enqueue_adjoint, req, gdst, dst_stride, gsrc, src_stride, layout);
+}
+
+int aai_adjoint_prepare(const aai_request *req)
+{
     aai::Geometry g;
-    AAI_TRY(check_adjoint(req, 1, gdst, dst_stride, gsrc, src_stride, g));
+    AAI_TRY(check_adjoint_request(req, 1, g));
     AAI_TRY(require_device());
-    DeviceBuffer dGdst, dGsrc;
-    hipStream_t stream = nullptr;
-    AAI_HIP(dGdst.alloc(sizeof(float) * (size_t)g.dW * g.dH));
-    AAI_HIP(dGsrc.alloc(sizeof(float) * (size_t)g.W * g.H));
-    AAI_HIP(upload(dGdst, gdst, dst_stride, g.dW, g.dH, sizeof(float)));
-    AAI_TRY(enqueue_adjoint(*req, g, 1, dGdst.as<const float>(), g.dW, 0, dGsrc.as<float>(), g.W, 0, stream));
-    AAI_HIP(hipStreamSynchronize(stream));
-    AAI_HIP(download(gsrc, src_stride, dGsrc, g.W, g.H, sizeof(float)));
-    return finish(*req, g, layout);
+    AAI_TRY(enqueue_adjoint_planned(*req, g, 0, nullptr, 0, 0, nullptr, 0, 0, nullptr));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_adjoint_planned_batch_device_f32(const aai_request *req, int32_t batch,
+                                         const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                         float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    return adjoint_device(enqueue_adjoint_planned, req, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
+}
+
+int aai_adjoint_planned_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
+{
+    return adjoint_host(enqueue_adjoint_planned, req, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
 int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)

@@ -491,9 +491,9 @@ std::string plan_description(const aai_request &rq, int channels)
         if (p.device == dev && p.band0 < 0 && (rotated || p.channels == channels) && p.built && same_request(p.key, rq)) {
             char buf[256];
             // (swap=0: the grid-order field stays in the format that bench.py, the tests and the recorded profiles read)
-            snprintf(buf, sizeof buf, "kernel=%d rows=%d nt=%d swap=0 tune=%s flagged=%u dense=%d form=%s build_ms=%.3f", p.kernel, p.tuneRows, p.tuneNt,
+            snprintf(buf, sizeof buf, "kernel=%d rows=%d nt=%d swap=0 tune=%s flagged=%u dense=%d form=%s build_ms=%.3f adjoint=%s", p.kernel, p.tuneRows, p.tuneNt,
                      p.tuneSource == 1 ? "measured" : (p.tuneSource == 2 ? "cached" : "default"), p.flaggedPixels, p.dense ? 1 : 0,
-                     p.kernel == AAI_KERNEL_ROTATED ? (p.form == aai::ROT_FORM_CELL ? "cell" : "quad") : "-", p.buildMs);
+                     p.kernel == AAI_KERNEL_ROTATED ? (p.form == aai::ROT_FORM_CELL ? "cell" : "quad") : "-", p.buildMs, p.adjState == 1 ? "tables" : "none");
             return std::string(buf);
         }
     }
@@ -577,6 +577,25 @@ int enqueue(const aai_request &rq, const aai::Geometry &g, int batch, const void
     return AAI_OK;
 }
 
+// the adjoint's scratch pool of a device, created on first need
+static int adjoint_scratch_pool(int device, hipMemPool_t *out)
+{
+    DevicePool &pool = device_pool(device);
+    std::lock_guard<std::mutex> lock(pool.m);
+    if (!pool.scratch) {
+        hipMemPoolProps props{};
+        props.allocType = hipMemAllocationTypePinned;
+        props.location.type = hipMemLocationTypeDevice;
+        props.location.id = device;
+        AAI_HIP(hipMemPoolCreate(&pool.scratch, &props));
+        uint64_t keep = UINT64_MAX;
+        const hipError_t ea = hipMemPoolSetAttribute(pool.scratch, hipMemPoolAttrReleaseThreshold, &keep);
+        if (ea != hipSuccess) { (void)hipMemPoolDestroy(pool.scratch); pool.scratch = nullptr; return hip_fail(ea, "hipMemPoolSetAttribute"); }
+    }
+    *out = pool.scratch;
+    return AAI_OK;
+}
+
 int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
                     float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
 {
@@ -590,19 +609,8 @@ int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const f
     AAI_HIP(hipGetDevice(&device));
     hipMemPool_t scratch = nullptr;
     {
-        DevicePool &pool = device_pool(device);
-        std::lock_guard<std::mutex> lock(pool.m);
-        if (!pool.scratch) {
-            hipMemPoolProps props{};
-            props.allocType = hipMemAllocationTypePinned;
-            props.location.type = hipMemLocationTypeDevice;
-            props.location.id = device;
-            AAI_HIP(hipMemPoolCreate(&pool.scratch, &props));
-            uint64_t keep = UINT64_MAX;
-            const hipError_t ea = hipMemPoolSetAttribute(pool.scratch, hipMemPoolAttrReleaseThreshold, &keep);
-            if (ea != hipSuccess) { (void)hipMemPoolDestroy(pool.scratch); pool.scratch = nullptr; return hip_fail(ea, "hipMemPoolSetAttribute"); }
-        }
-        scratch = pool.scratch;
+        const int rc = adjoint_scratch_pool(device, &scratch);
+        if (rc != AAI_OK) return rc;
     }
     double *n = nullptr;
     AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
@@ -613,6 +621,113 @@ int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const f
     const hipError_t ef = hipFreeAsync(n, stream);
     g_lastKernel = name;
     if (e != hipSuccess) return hip_fail(e, name);
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    return AAI_OK;
+}
+
+// The adjoint tables of an axis plan (Plan::adjState): the inverse ranges of its two tables and, where it has flagged pixels, the
+// lists of the correction pass.  Under p.build; blocks (uploads on the device pool's build stream, the flagged list read back).
+static int build_adjoint_tables(Plan &p)
+{
+    if (p.adjState) return AAI_OK;
+    if (p.kernel != AAI_KERNEL_AXIS || p.dense || p.channels != 1 || p.band0 >= 0) { p.adjState = 2; return AAI_OK; }
+    const aai::Geometry &g = p.g;
+    std::vector<aai::AxisRange> cols, rows;
+    if (!aai::build_axis_adjoint_ranges(p.tabs, g.W, g.H, cols, rows)) { p.adjState = 2; return AAI_OK; }
+    hipStream_t bs = nullptr;
+    AAI_HIP(pool_build_stream(device_pool(p.device), &bs));
+    std::vector<std::pair<int, int>> srcList, dstList, flagged;
+    std::vector<int> grazedCols, grazedRows;
+    aai::axis_grazed_indices(p.tabs.lane, grazedCols);
+    aai::axis_grazed_indices(p.tabs.row, grazedRows);
+    if (p.flaggedPixels) {
+        std::vector<uint2> flaggedDev(p.flaggedPixels);
+        AAI_HIP(hipMemcpyAsync(flaggedDev.data(), p.dList, flaggedDev.size() * sizeof(uint2), hipMemcpyDeviceToHost, bs));
+        AAI_HIP(hipStreamSynchronize(bs));
+        flagged.resize(flaggedDev.size());
+        for (size_t i = 0; i < flaggedDev.size(); ++i) flagged[i] = std::make_pair((int)flaggedDev[i].x, (int)flaggedDev[i].y);
+    }
+    if (!flagged.empty() || !grazedCols.empty() || !grazedRows.empty()) {
+        // (a correction pass over more than half of the source image is the general adjoint with a detour)
+        const aai::RotLaunch r = aai::make_rot_launch(g, p.key.mode, p.key.policy);
+        if (!aai::build_adjoint_lists(r, flagged, grazedCols, grazedRows, (size_t)g.W * g.H / 2, srcList, dstList)) { p.adjState = 2; return AAI_OK; }
+    }
+    std::vector<uint2> src2(srcList.size()), dst2(dstList.size());
+    for (size_t i = 0; i < srcList.size(); ++i) src2[i] = make_uint2((unsigned)srcList[i].first, (unsigned)srcList[i].second);
+    for (size_t i = 0; i < dstList.size(); ++i) dst2[i] = make_uint2((unsigned)dstList[i].first, (unsigned)dstList[i].second);
+    auto upload = [&](const void *h, size_t bytes, void **d) -> hipError_t {
+        if (!bytes) { *d = nullptr; return hipSuccess; }
+        hipError_t e = hipMalloc(d, bytes);
+        if (e != hipSuccess) return e;
+        return hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, bs);      // (the host vectors outlive the copy: synchronised below)
+    };
+    hipError_t e = upload(cols.data(), cols.size() * sizeof(aai::AxisRange), (void **)&p.dColRange);
+    if (e == hipSuccess) e = upload(rows.data(), rows.size() * sizeof(aai::AxisRange), (void **)&p.dRowRange);
+    if (e == hipSuccess) e = upload(src2.data(), src2.size() * sizeof(uint2), &p.dAdjSrcList);
+    if (e == hipSuccess) e = upload(dst2.data(), dst2.size() * sizeof(uint2), &p.dAdjDstList);
+    const hipError_t es = hipStreamSynchronize(bs);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        for (void **d : {(void **)&p.dColRange, (void **)&p.dRowRange, &p.dAdjSrcList, &p.dAdjDstList})
+            if (*d) { (void)hipFree(*d); *d = nullptr; }
+        return hip_fail(e, "uploading the adjoint tables");             // (adjState stays 0: a later call tries again)
+    }
+    p.adjSrcCount = (unsigned)src2.size(); p.adjDstCount = (unsigned)dst2.size();
+    p.adjState = 1;
+    return AAI_OK;
+}
+
+int enqueue_adjoint_planned(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
+                            float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+{
+    const bool prepareOnly = dGdst == nullptr;
+    PlanRef p;
+    if (pick_kernel(rq, g) == AAI_KERNEL_AXIS) {
+        // the forward's plan under the forward's key (a packed fp32 image, one channel, the whole image)
+        const int rc = acquire_plan(rq, g, -1, -1, 1, aai::ROT_FORM_QUAD, &p, /*onCallerStream*/ !prepareOnly, stream);
+        if (rc != AAI_OK) return rc;
+        std::lock_guard<std::mutex> lock(p->build);
+        const int rt = build_adjoint_tables(*p);
+        if (rt != AAI_OK) return rt;
+        if (p->adjState != 1) p.reset();
+    }
+    if (prepareOnly) return AAI_OK;
+    if (!p) return enqueue_adjoint(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+
+    std::lock_guard<std::mutex> lock(p->launch);
+    const aai::AxisLaunch f = make_axis_launch(*p, 1, dstStride);
+    aai::AxisAdjointLaunch a{};
+    a.laneTab = p->dLane; a.rowTab = p->dRow; a.colRange = p->dColRange; a.rowRange = p->dRowRange;
+    a.srcW = g.W; a.srcH = g.H;
+    a.outBase = f.outBase; a.outStrideA = f.outStrideA; a.outStrideB = f.outStrideB;
+    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
+    const bool listed = p->adjSrcCount != 0 && p->adjDstCount != 0;
+    g_lastKernel = listed ? "aai_axis_adjoint_kernel+listed" : "aai_axis_adjoint_kernel";
+    // the correction pass's scratch: one fp64 image of the dst size per image in flight, as in enqueue_adjoint -- only where there is a list
+    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * sizeof(double);
+    int chunk = std::min(batch, kMaxGridZ);
+    double *n = nullptr;
+    aai::RotLaunch r{};
+    if (listed) {
+        r = aai::make_rot_launch(g, rq.mode, rq.policy);
+        chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk, ((size_t)1 << 30) / imageBytes));
+        hipMemPool_t scratch = nullptr;
+        const int rc = adjoint_scratch_pool(p->device, &scratch);
+        if (rc != AAI_OK) return rc;
+        AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
+    }
+    hipError_t e = hipSuccess;
+    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
+        const int nb = std::min(batch - b0, chunk);
+        const float *gd = dGdst + (int64_t)b0 * dstImageStride;
+        float *gs = dGsrc + (int64_t)b0 * srcImageStride;
+        e = aai::launch_axis_adjoint(a, nb, gd, dv, gs, sv, stream, nullptr);
+        if (e == hipSuccess && listed)
+            e = aai::launch_adjoint_listed(r, nb, gd, dv, n, gs, sv, static_cast<const uint2 *>(p->dAdjDstList), p->adjDstCount,
+                                           static_cast<const uint2 *>(p->dAdjSrcList), p->adjSrcCount, stream);
+    }
+    const hipError_t ef = n ? hipFreeAsync(n, stream) : hipSuccess;
+    if (e != hipSuccess) return hip_fail(e, "aai_axis_adjoint_kernel");
     if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     return AAI_OK;
 }

@@ -54,6 +54,13 @@ struct Plan {
     unsigned *dTileFlags = nullptr;  // (into dScan) one bit per 16 x 16 tile with a flagged pixel (aai::launch_tile_flags), tileFlagWords words per tile row
     int tileFlagWords = 0;
     int *dLive = nullptr;            // per-pixel kernels on a rotated canvas: live tile span per tile row (aai::rotated_live_spans), or none
+    // the transposed K1 (aai_adjoint_planned_*): built by the first planned adjoint of the plan or by aai_adjoint_prepare, under `build`.
+    // adjState: 0 = not asked for yet, 1 = tables on the device, 2 = this plan keeps the general adjoint (wide or dense plan, a
+    // table the inversion's check refuses, a correction list that would cover most of the image)
+    int adjState = 0;
+    aai::AxisRange *dColRange = nullptr, *dRowRange = nullptr;
+    void *dAdjSrcList = nullptr, *dAdjDstList = nullptr;      // uint2 (x, y): the source pixels the general adjoint recomputes, the dst pixels it reads
+    unsigned adjSrcCount = 0, adjDstCount = 0;
     double buildMs = 0.0;            // wall clock of build_plan (tables, scans, launch-shape measurement)
     // Built once, by whoever gets here first, under `build` -- NOT under the cache's lock: other requests, other devices
     // and other threads are not held up by this plan's scans or launch-shape measurement.  `launch` serialises the launches of a
@@ -70,6 +77,10 @@ struct Plan {
         if (dLane) (void)hipFree(dLane);
         if (dRow) (void)hipFree(dRow);
         if (dStrips) (void)hipFree(dStrips);
+        if (dColRange) (void)hipFree(dColRange);
+        if (dRowRange) (void)hipFree(dRowRange);
+        if (dAdjSrcList) (void)hipFree(dAdjSrcList);
+        if (dAdjDstList) (void)hipFree(dAdjDstList);
     }
 };
 typedef std::shared_ptr<Plan> PlanRef;
@@ -113,12 +124,19 @@ int resolved_kernel(const aai_request &rq, const Geometry &g);      // pick_kern
 void fill_layout(const Geometry &g, int kernel, aai_layout *out);
 int require_device();
 
+// The planned adjoint (aai_adjoint_planned_*; the caller has checked the arguments).  Axis-aligned requests whose plan is neither
+// wide nor dense: the forward's plan (looked up with the forward's key, built like aai_prepare builds it when missing) with its
+// adjoint tables (built on first need: blocks), then aai_axis_adjoint_kernel and, where the plan has flagged pixels, the listed
+// passes of the general adjoint behind it.  Every other request: enqueue_adjoint.  dGdst == NULL: prepare only (aai_adjoint_prepare).
+int enqueue_adjoint_planned(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
+                            float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
+
 // Finds the plan for (request, current device) or inserts a fresh one, then builds it if nobody has (blocking: table
 // uploads, the one-off scans, K1's launch-shape measurement -- on `stream` when the caller has one to give (onCallerStream; a
 // stream that is being captured into a graph is not used), else on the device pool's build stream).
 // form: aai::RotForm of a rotated request's launch (rot_form below); ignored by the other kernels
 int acquire_plan(const aai_request &rq, const Geometry &g, int band0, int band1, int channels, int form, PlanRef *out, bool onCallerStream = false, hipStream_t stream = nullptr);
-// "kernel=K rows=R nt=N swap=0 tune=T flagged=F dense=D form=M build_ms=B" of the cached whole-image plan ("" when there is none)
+// "kernel=K rows=R nt=N swap=0 tune=T flagged=F dense=D form=M build_ms=B adjoint=tables|none" of the cached whole-image plan ("" when there is none)
 std::string plan_description(const aai_request &rq, int channels);
 // which fp32 formulation serves a launch of this request: the cell formulation takes plain images below 4 GiB in area mode
 int rot_form(const aai_request &rq, const Geometry &g, int channels, int srcType, int64_t srcStride);

@@ -115,6 +115,24 @@ hipError_t launch_cell(const RotLaunch &r, const QuadMap &m, const void *src, in
 hipError_t launch_adjoint(const RotLaunch &r, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
                           hipStream_t stream, const char **kernelName);
 
+// the same two passes over LISTS of pixels (the correction pass behind the transposed separable kernel): pass 1 over the nDst dst
+// pixels of dstList into n (the other elements of n are neither written nor read), pass 2 over the nSrc source pixels of srcList,
+// whose gsrc it OVERWRITES.  The lists hold every dst pixel pass 2 reads (build_adjoint_lists).  `batch` <= 65535.
+hipError_t launch_adjoint_listed(const RotLaunch &r, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
+                                 const uint2 *dstList, unsigned nDst, const uint2 *srcList, unsigned nSrc, hipStream_t stream);
+
+// ---- the transpose of K1 (aai_axis_adjoint.hip): the adjoint at rotations by multiples of 90 degrees, fp32, from the forward's tables
+struct AxisAdjointLaunch {
+    const AxisEntry *laneTab;   // the forward plan's tables (device)
+    const AxisEntry *rowTab;
+    const AxisRange *colRange;  // device, srcW entries: the lane-axis outputs that read source column sx
+    const AxisRange *rowRange;  // device, srcH entries: the row-axis outputs that read source row sy
+    int srcW, srcH;
+    int64_t outBase, outStrideA, outStrideB;   // gdst element of (ka, kb) = outBase + ka*outStrideA + kb*outStrideB (the forward's mapping)
+};
+hipError_t launch_axis_adjoint(const AxisAdjointLaunch &a, int batch, const float *gdst, ImageView dv, float *gsrc, ImageView sv,
+                               hipStream_t stream, const char **kernelName);
+
 // ---- utilities -----------------------------------------------------------------------------------------
 hipError_t launch_synth(float *dst, int W, int H, int64_t stride, uint64_t seed, hipStream_t stream);
 hipError_t launch_synth_rows(float *dst, int W, int H, int row0, int row1, int64_t stride, uint64_t seed, hipStream_t stream);

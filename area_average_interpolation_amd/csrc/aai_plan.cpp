@@ -5,6 +5,7 @@
 #include "aai_rot_cell.hpp"
 #include "aai_axis_verify.hpp"
 #include "aai_axis_verify.hpp"
+#include "aai_adjoint_math.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -593,5 +594,105 @@ bool axis_verify_by_class(const RotLaunch &r, std::vector<std::pair<int, int>> &
     return true;
 }
 
+
+// ---- the transpose of K1: inverse tables and the lists of the correction pass ----------------------------------------
+static bool invert_axis_table(const std::vector<AxisEntry> &tab, int n, std::vector<AxisRange> &out)
+{
+    out.assign((size_t)n, AxisRange{1, 0});
+    for (int k = 0; k < (int)tab.size(); ++k) {
+        const AxisEntry &e = tab[k];
+        if (e.wFirst == 0.f && e.wMid == 0.f && e.wLast == 0.f) continue;       // a dst pixel off the image: a zero row of W
+        if (e.s0 < 0 || e.s1 < e.s0 || e.s1 >= n) return false;
+        for (int s = e.s0; s <= e.s1; ++s) {
+            AxisRange &r = out[(size_t)s];
+            if (r.k0 > r.k1) r.k0 = r.k1 = k;
+            else if (r.k1 + 1 == k) r.k1 = k;
+            else return false;                                                   // not consecutive: the windows are not monotone
+        }
+    }
+    return true;
+}
+
+bool build_axis_adjoint_ranges(const AxisTables &t, int W, int H, std::vector<AxisRange> &cols, std::vector<AxisRange> &rows)
+{
+    if (t.channels != 1 || t.wide || (int)t.lane.size() != t.nA || (int)t.row.size() != t.nB) return false;
+    return invert_axis_table(t.lane, W, cols) && invert_axis_table(t.row, H, rows);
+}
+
+void axis_grazed_indices(const std::vector<AxisEntry> &tab, std::vector<int> &grazed)
+{
+    constexpr float kGrazed = 1e-9f;
+    grazed.clear();
+    for (const AxisEntry &e : tab) {
+        if (e.wFirst == 0.f && e.wMid == 0.f && e.wLast == 0.f) continue;
+        if (e.wFirst < kGrazed) grazed.push_back(e.s0);
+        if (e.s1 > e.s0 && e.wLast < kGrazed) grazed.push_back(e.s1);
+    }
+    std::sort(grazed.begin(), grazed.end());
+    grazed.erase(std::unique(grazed.begin(), grazed.end()), grazed.end());
+}
+
+bool build_adjoint_lists(const RotLaunch &r, const std::vector<std::pair<int, int>> &flagged, const std::vector<int> &grazedCols,
+                         const std::vector<int> &grazedRows, size_t maxSource,
+                         std::vector<std::pair<int, int>> &srcList, std::vector<std::pair<int, int>> &dstList)
+{
+    srcList.clear(); dstList.clear();
+    if (flagged.empty() && grazedCols.empty() && grazedRows.empty()) return true;
+    std::vector<unsigned char> inSrc((size_t)r.W * r.H, 0), inDst((size_t)r.dW * r.dH, 0);
+    size_t nSrc = 0;
+    auto mark = [&](int sx, int sy) {
+        unsigned char &m = inSrc[(size_t)sy * r.W + sx];
+        if (!m) { m = 1; ++nSrc; }
+        return nSrc <= maxSource;
+    };
+    for (int sx : grazedCols)
+        for (int sy = 0; sx >= 0 && sx < r.W && sy < r.H; ++sy)
+            if (!mark(sx, sy)) return false;
+    for (int sy : grazedRows)
+        for (int sx = 0; sy >= 0 && sy < r.H && sx < r.W; ++sx)
+            if (!mark(sx, sy)) return false;
+    for (const auto &d : flagged) {
+        double px, py;
+        pixel_centre(r, d.first, d.second, px, py);
+        int x0, x1, y0, y1;
+        rot_window(r, px, py, x0, x1, y0, y1);
+        for (int Y = y0; Y <= y1; ++Y)
+            for (int X = x0; X <= x1; ++X) {
+                // virtual pixel -> source pixel: the inverse of adjoint_virtual_pixel
+                int vx, vy;
+                switch (r.quadrant) {
+                default:
+                case 0: vx = X;            vy = Y;            break;
+                case 1: vx = Y;            vy = r.mW - 1 - X; break;
+                case 2: vx = r.mW - 1 - X; vy = r.mH - 1 - Y; break;
+                case 3: vx = r.mH - 1 - Y; vy = X;            break;
+                }
+                const int sx = vx / r.scale, sy = vy / r.scale;
+                if (vx < 0 || vy < 0 || sx >= r.W || sy >= r.H) continue;
+                if (!mark(sx, sy)) return false;
+            }
+    }
+    const double R = adjoint_reach(r), rL = 1.0 / r.side;
+    srcList.reserve(nSrc);
+    for (int sy = 0; sy < r.H; ++sy)
+        for (int sx = 0; sx < r.W; ++sx) {
+            if (!inSrc[(size_t)sy * r.W + sx]) continue;
+            srcList.emplace_back(sx, sy);
+            for (int jy = 0; jy < r.scale; ++jy)
+                for (int jx = 0; jx < r.scale; ++jx) {
+                    int X, Y, dxa, dxb, dya, dyb;
+                    adjoint_virtual_pixel(r, sx, sy, jx, jy, X, Y);
+                    if (!adjoint_candidates(r, X, Y, R, rL, dxa, dxb, dya, dyb)) continue;
+                    dxa = std::max(dxa - 1, 0); dxb = std::min(dxb + 1, r.dW - 1);
+                    dya = std::max(dya - 1, 0); dyb = std::min(dyb + 1, r.dH - 1);
+                    for (int dy = dya; dy <= dyb; ++dy)
+                        for (int dx = dxa; dx <= dxb; ++dx) inDst[(size_t)dy * r.dW + dx] = 1;
+                }
+        }
+    for (int dy = 0; dy < r.dH; ++dy)
+        for (int dx = 0; dx < r.dW; ++dx)
+            if (inDst[(size_t)dy * r.dW + dx]) dstList.emplace_back(dx, dy);
+    return true;
+}
 
 }  // namespace aai

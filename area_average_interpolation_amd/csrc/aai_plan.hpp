@@ -130,6 +130,31 @@ struct AxisTables {
 void build_axis_tables(const Geometry &g, int mode, AxisTables &t, int channels = 1);
 void restrict_axis_tables_to_band(const Geometry &g, AxisTables &t, int row0, int row1, int &srcRow0, int &srcRow1, int extraRows = 0);
 
+// ---- the transpose of K1 (aai_axis_adjoint.hip) ------------------------------------------------------------
+// Output indices [k0, k1] (inclusive) along one axis whose window holds a given source index; k0 > k1: no dst pixel reads it.
+struct AxisRange { int32_t k0, k1; };
+static_assert(sizeof(AxisRange) == 8, "AxisRange layout");
+
+// Inverts the two tables of a whole-image, single-channel plan: one range per source column (from t.lane) and per source row
+// (from t.row).  Windows are monotone in the output index, so the outputs that read a source index are consecutive; this is
+// CHECKED entry by entry (every k of a range is a non-empty entry whose window holds the index, every window lies in the
+// image), and false is returned where it does not hold -- the caller then keeps the general adjoint.
+bool build_axis_adjoint_ranges(const AxisTables &t, int W, int H, std::vector<AxisRange> &cols, std::vector<AxisRange> &rows);
+
+// Source indices along one axis that some window of the table only GRAZES: its first or last weight is below 1e-9 of the dst pixel's
+// total, a rounding residue of an edge that should lie on the pixel boundary.  Whether such a residue counts is a decision of the
+// reference's classifier, taken pair by pair (the forward's tolerance does not see 1e-16; the adjoint's exact zeros do), so the
+// source pixels of these rows and columns are left to the general adjoint (build_adjoint_lists).
+void axis_grazed_indices(const std::vector<AxisEntry> &tab, std::vector<int> &grazed);
+
+// The pixels the general adjoint recomputes behind the transposed separable kernel.  srcList = every source pixel inside the window
+// (rot_window) of a flagged dst pixel (dx, dy) of the plan, and every pixel of the grazed source rows and columns; dstList = every
+// dst pixel the general gather visits for a pixel of srcList (adjoint_gather's own candidate box, one more pixel on every side).
+// Both deduplicated, (x, y) pairs in row-major order.  False when srcList would exceed maxSource pixels (the lists are then empty).
+bool build_adjoint_lists(const RotLaunch &r, const std::vector<std::pair<int, int>> &flagged, const std::vector<int> &grazedCols,
+                         const std::vector<int> &grazedRows, size_t maxSource,
+                         std::vector<std::pair<int, int>> &srcList, std::vector<std::pair<int, int>> &dstList);
+
 // K1's separable model checked on the host, one representative per (column class, row class), where the geometry's
 // arithmetic is exact (aai_plan.cpp); false = does not qualify, run the device scan.  flagged: (dx, dy) of the dst pixels
 // the fix-up pass must recompute; dense: more than maxListed of them.

@@ -2,7 +2,8 @@
 
 ``resample(x, ...)`` runs the library's forward (aai_resample_batch_device_f32) on a device-resident fp32 tensor and is a
 ``torch.autograd.Function``: its backward is the library's adjoint (aai_adjoint_batch_device_f32), gsrc = W^T gdst with the
-forward's own weights -- not an approximation through ``grid_sample``.  Both launch on ``torch.cuda.current_stream()`` of the
+forward's own weights -- not an approximation through ``grid_sample`` (``planned_backward=True``: the planned adjoint,
+aai_adjoint_planned_batch_device_f32).  Both launch on ``torch.cuda.current_stream()`` of the
 tensor's device and only enqueue work.
 
 torch is imported here, not by the package: ``import area_average_interpolation_amd`` works without it.
@@ -25,15 +26,30 @@ def _ensure_prepared(rq):
     api.prepare(rq)
 
 
+def _ensure_adjoint_prepared(rq):
+    """The planned adjoint's first call per (geometry, device) builds the plan's adjoint tables and synchronises
+    (aai_adjoint_prepare): do that in the forward, outside any stream capture.  Only a separable (kernel=1), non-dense plan can
+    hold such tables; every other plan's backward runs the general kernels, which need none."""
+    tokens = api.plan_shape(rq).split()
+    if "kernel=%d" % L.KERNEL_AXIS not in tokens or "dense=0" not in tokens or "adjoint=none" not in tokens:
+        return
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("resample(planned_backward=True): this geometry has no adjoint tables on this device yet and the current "
+                           "stream is being captured; call resample() (or adjoint_prepare()) once with the same geometry before capturing")
+    api.adjoint_prepare(rq)
+
+
 class _Resample(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, rq, lay):
+    def forward(ctx, x, rq, lay, planned):
         B, H, W = x.shape
         y = torch.empty((B, lay.dst_height, lay.dst_width), dtype=torch.float32, device=x.device)
-        ctx.rq, ctx.src_shape = rq, (B, H, W)
+        ctx.rq, ctx.src_shape, ctx.planned = rq, (B, H, W), planned
         if B:
             with torch.cuda.device(x.device):
                 _ensure_prepared(rq)
+                if planned and ctx.needs_input_grad[0]:
+                    _ensure_adjoint_prepared(rq)
                 api.resample_device(rq, x.data_ptr(), W, y.data_ptr(), lay.dst_width, stream=torch.cuda.current_stream().cuda_stream,
                                     batch=B, src_image_stride=H * W, dst_image_stride=lay.dst_height * lay.dst_width)
         return y
@@ -50,16 +66,24 @@ class _Resample(torch.autograd.Function):
             dH, dW = gy.shape[1], gy.shape[2]
             with torch.cuda.device(gy.device):
                 api.adjoint_device(ctx.rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
-                                   batch=B, dst_image_stride=dH * dW, src_image_stride=H * W)
-        return gx, None, None
+                                   batch=B, dst_image_stride=dH * dW, src_image_stride=H * W, planned=ctx.planned)
+        return gx, None, None, None
 
 
-def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
+def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
+             planned_backward=False):
     """Resample a CUDA/HIP fp32 tensor of shape (H, W) or (B, H, W); returns ``(y, dst_isocenter)`` with y of shape
     (dH, dW) or (B, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
     bilinear / bicubic comparison paths have no adjoint: an x that requires grad raises ValueError there).  Non-contiguous
     input is made contiguous; other dtypes raise TypeError, CPU tensors and other ranks ValueError, an invalid geometry
-    AaiError."""
+    AaiError.
+
+    planned_backward: False (the default) -- the backward is aai_adjoint_batch_device_f32, the double-precision gather at every
+    rotation.  True -- the backward is aai_adjoint_planned_batch_device_f32: at rotations by multiples of 90 degrees the transposed
+    separable kernel on the forward's own plan (fp32 weights and sums, within a few 1e-7 relative of the default, and one to two
+    orders of magnitude faster there), the default's kernels and bits at every other rotation.  With True and an x that requires
+    grad the forward also builds the plan's adjoint tables (aai_adjoint_prepare; it synchronises once per geometry and device), so
+    inside a stream capture a geometry without them raises RuntimeError, like a geometry without a plan."""
     if not isinstance(x, torch.Tensor):
         raise TypeError("resample() takes a torch.Tensor")
     if x.dtype != torch.float32:
@@ -75,5 +99,5 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         raise api.AaiError(rc, msg)
     if xb.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
         raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
-    y = _Resample.apply(xb, rq, lay)
+    y = _Resample.apply(xb, rq, lay, bool(planned_backward))
     return (y if x.dim() == 3 else y.squeeze(0)), (lay.dst_iso_x, lay.dst_iso_y)

@@ -184,8 +184,9 @@ int aai_prepare(const aai_request *req, int32_t channels /* 1 for plain images; 
  *
  * aai_plan_info writes a one-line description of the cached whole-image plan of `req` on the current device into `text`
  * ("" when there is none yet): "kernel=K rows=R nt=N swap=0 tune=measured|cached|default flagged=F dense=D form=cell|quad|-
- * build_ms=B" -- the kernel family (AAI_KERNEL_*), K1's launch shape (swap is always 0) and where it came from, the dst pixels the
- * double-precision pass owns, the fp32 formulation of a rotated area request, and what building the plan cost. */
+ * build_ms=B adjoint=tables|none" -- the kernel family (AAI_KERNEL_*), K1's launch shape (swap is always 0) and where it came from,
+ * the dst pixels the double-precision pass owns, the fp32 formulation of a rotated area request, what building the plan cost, and
+ * whether the plan holds the tables of the planned adjoint (aai_adjoint_prepare; new tokens are appended at the end of the line). */
 int aai_plan_info(const aai_request *req, int32_t channels, char *text, int32_t capacity);
 /* Drops every cached plan (device tables, flag lists, side streams) while the HIP runtime is alive.  Optional: the cache is
  * never torn down from a static destructor, so a process may also simply exit. */
@@ -276,7 +277,8 @@ int aai_resample_band_device_f32(const aai_request *req, int32_t dst_row0, int32
  *   - Weights: every (dst, src) pair is evaluated in double precision by the per-pair code of the forward's fix-up pass,
  *     the replay of the reference's classifier at knife edges included; sums in double precision, ONE fp32 rounding of the
  *     result (~6e-8 relative).  One code path for every rotation: multiples of 90 degrees, where the separable kernel
- *     serves the forward, go through the same general kernels and are correspondingly slower than they could be.
+ *     serves the forward, go through the same general kernels and are correspondingly slower than they could be (the planned entries
+ *     below serve those rotations with the transposed separable kernel).
  *   - Cost: two kernels -- one lane per dst pixel (gdst / its total weight, into scratch), then one lane per SOURCE pixel
  *     that gathers from the dst pixels it feeds.  Each evaluates every overlapping pair once, with the knife-edge variant of
  *     the per-pair code for EVERY pair.  MEASURED on an MI355X (profiles/adjoint_time.txt, per kernel: profiles/
@@ -303,6 +305,10 @@ int aai_adjoint_batch_device_f32(const aai_request *req, int32_t batch,
 /* host buffers: upload gdst, run, download gsrc; `layout` may be NULL */
 int aai_adjoint_f32(const aai_request *req, const float *gdst, int64_t dst_stride,
                     float *gsrc, int64_t src_stride, aai_layout *layout);
+
+/* The PLANNED adjoint -- the transposed separable kernel at rotations by multiples of 90 degrees, on the forward's cached plan, one to
+ * two orders of magnitude faster there -- is declared and documented in include/aai_adjoint_planned.h (an extension header over
+ * this one; the entries above are unchanged). */
 
 /* ---- synthetic input ------------------------------------------------------------
  * Fill a device image with the stateless-hash fp32 uniform [0,1) pattern used by every benchmark and

@@ -4,7 +4,11 @@ does the same double-precision pair evaluations once per pair -- on the geometri
 A fresh child process per geometry; in it 3 warm-up launches of each, then N (default 24) timed launches of each between
 device events, forward and adjoint alternating; reported: median, 10th..90th percentile, and the ratio of the medians.
 
-usage: python tools/adjoint_time.py [--launches N] [--out FILE]      (the table also goes to stdout)"""
+--planned: the rotations by multiples of 90 degrees instead (PLANNED_GEOMETRIES), three launches taking turns -- the forward (the
+separable kernel), the general adjoint and the planned adjoint (aai_adjoint_planned_batch_device_f32, after aai_adjoint_prepare) --
+with the largest deviation of the planned from the general result relative to max(|general|, 1e-3 max|general|) at the end of each row.
+
+usage: python tools/adjoint_time.py [--planned] [--launches N] [--out FILE]      (the table also goes to stdout)"""
 import argparse
 import os
 import subprocess
@@ -16,6 +20,51 @@ sys.path.insert(0, ROOT)
 # (name, W, H, srcRes, dstRes, angle)
 GEOMETRIES = [("cfg3", 8192, 8192, 8192.0, 2731.0, 17.5), ("wide8", 8192, 8192, 8.0, 1.0, 17.5), ("up2", 2048, 2048, 1.0, 2.0, 30.0),
               ("axis4", 4096, 4096, 4.0, 1.0, 0.0), ("quarter2.5", 4096, 4096, 2.5, 1.0, 90.0)]
+# the planned adjoint's rows: the two axis rows above, a flipped quadrant and a transposed up-sampling
+PLANNED_GEOMETRIES = [GEOMETRIES[3], GEOMETRIES[4], ("half180", 4096, 4096, 2.0, 1.0, 180.0), ("up2x270", 2048, 2048, 1.0, 2.0, 270.0)]
+
+
+def child_planned(name, mode, launches):
+    import numpy as np
+    import torch
+    import area_average_interpolation_amd as aai
+    aai.set_device(0)
+    _, W, H, sr, dr, ang = [g for g in PLANNED_GEOMETRIES if g[0] == name][0]
+    rq = aai.make_request(W, H, sr, dr, ((W - 1) / 2, (H - 1) / 2), ang, mode=mode)
+    lay = aai.query(rq)[2]
+    dW, dH = lay.dst_width, lay.dst_height
+    st = torch.cuda.current_stream().cuda_stream
+    x = torch.empty((H, W), dtype=torch.float32, device="cuda")
+    y = torch.empty((dH, dW), dtype=torch.float32, device="cuda")
+    aai.synth_device(x.data_ptr(), W, H, W, 1, st)
+    aai.synth_device(y.data_ptr(), dW, dH, dW, 2, st)
+    wx, general, planned = torch.empty_like(y), torch.empty_like(x), torch.empty_like(x)
+    aai.adjoint_prepare(rq)
+    runs = {"fwd": lambda: aai.resample_device(rq, x.data_ptr(), W, wx.data_ptr(), dW, st),
+            "general": lambda: aai.adjoint_device(rq, y.data_ptr(), dW, general.data_ptr(), W, st),
+            "planned": lambda: aai.adjoint_device(rq, y.data_ptr(), dW, planned.data_ptr(), W, st, planned=True)}
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    kernel = aai.last_kernel()
+    times = {k: [] for k in runs}
+    for _ in range(launches):
+        for key, fn in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[key].append(a.elapsed_time(b))
+    gd = general.double()
+    dev = float(((planned.double() - gd).abs() / gd.abs().clamp_min(1e-3 * float(gd.abs().max()))).max())
+    t = {k: np.array(v) for k, v in times.items()}
+    cell = lambda v: "%8.3f ms (%.3f..%.3f)" % (np.median(v), np.percentile(v, 10), np.percentile(v, 90))
+    print("%-10s %-4s %5dx%-5d -> %5dx%-5d  forward %s  general adjoint %s  planned adjoint %s  general/planned %6.1f  planned/forward %5.2f  deviation %.2e  [%s; %s]" % (
+        name, "area" if mode == aai.MODE_AREA else "fast", W, H, dW, dH, cell(t["fwd"]), cell(t["general"]), cell(t["planned"]),
+        np.median(t["general"]) / np.median(t["planned"]), np.median(t["planned"]) / np.median(t["fwd"]), dev, kernel,
+        " ".join(tok for tok in aai.plan_shape(rq).split() if tok.split("=")[0] in ("flagged", "dense", "adjoint"))), flush=True)
 
 
 def child(name, mode, launches):
@@ -70,19 +119,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=24)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--planned", action="store_true")
     ap.add_argument("--child", nargs=2, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.launches < 20:
         ap.error("at least 20 timed launches")
     if args.child:
-        child(args.child[0], int(args.child[1]), args.launches)
+        (child_planned if args.planned else child)(args.child[0], int(args.child[1]), args.launches)
         return 0
-    lines = ["# median (10th..90th percentile) of %d launches each, device events, forward and adjoint alternating, one process per row" % args.launches]
+    lines = ["# median (10th..90th percentile) of %d launches each, device events, %s, one process per row"
+             % (args.launches, "forward, general adjoint and planned adjoint taking turns" if args.planned else "forward and adjoint alternating")]
     print(lines[0], flush=True)
-    for g in GEOMETRIES:
+    for g in (PLANNED_GEOMETRIES if args.planned else GEOMETRIES):
         for mode in (1, 2):
             # a fresh process per row, under its own time limit; a row that fails ends the run
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--launches", str(args.launches), "--child", g[0], str(mode)],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--launches", str(args.launches), "--child", g[0], str(mode)] + (["--planned"] if args.planned else []),
                                capture_output=True, text=True, timeout=240)
             if r.returncode != 0:
                 sys.stderr.write(r.stdout + r.stderr)

@@ -96,6 +96,12 @@ PLANNED_SYMBOLS = {
     "aai_adjoint_planned_f32": (ctypes.c_int, [_RQ, _P, _I64, _P, _I64, _LY]),
 }
 
+# the extension header include/aai_adjoint_interleaved.h
+INTERLEAVED_ADJOINT_SYMBOLS = {
+    "aai_adjoint_interleaved_device_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_adjoint_interleaved_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
+}
+
 _lib = None
 
 
@@ -116,7 +122,7 @@ def load():
             except ImportError:
                 pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()) + list(INTERLEAVED_ADJOINT_SYMBOLS.items()):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

@@ -321,6 +321,44 @@ def adjoint_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter,
     return rc, "", gsrc
 
 
+def adjoint_interleaved_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None,
+                               dst_image_stride=0, src_image_stride=0):
+    """aai_adjoint_interleaved_device_f32: gsrc = W(request)^T gdst per channel on device-resident fp32 images with `channels` (1..4)
+    interleaved channels -- the transpose of what resample_interleaved_device computes (area and fast modes).  Element (x, y, c) of
+    image b at b * image_stride + y * stride + x * channels + c; raw device pointers (ints), strides in elements, a hipStream_t
+    handle.  Channel c gets the bits adjoint_device gives plane c alone; a pair's weight is computed once for all channels."""
+    rc = L.load().aai_adjoint_interleaved_device_f32(_ref(request), 1 if batch is None else int(batch), int(channels), gdst_ptr, dst_stride,
+                                                     dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def adjoint_interleaved_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle,
+                             mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
+    """Host-buffer interleaved adjoint (aai_adjoint_interleaved_f32): gdst is the [dH, dW, C] gradient with respect to the output of
+    resample_interleaved_host(src of shape (H, W, C), ...), src_shape = (H, W) or (H, W, C); returns (code, message, gsrc [H, W, C]
+    float32 or None)."""
+    lib = L.load()
+    g = np.ascontiguousarray(gdst, dtype=np.float32)
+    if g.ndim != 3:
+        raise ValueError("gdst must be a [dH, dW, C] array")
+    C = g.shape[2]
+    if len(src_shape) == 3 and int(src_shape[2]) != C:
+        raise ValueError("gdst has %d channels, src_shape %d" % (C, int(src_shape[2])))
+    H, W = int(src_shape[0]), int(src_shape[1])
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None
+    if g.shape[:2] != (lay.dst_height, lay.dst_width):
+        raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width, C),))
+    gsrc = np.empty((H, W, C), dtype=np.float32)
+    rc = lib.aai_adjoint_interleaved_f32(_ref(rq), C, g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
+    if rc != L.OK:
+        return rc, last_error(), None
+    return rc, "", gsrc
+
+
 def resample_multi_device(request, shards, src_stride, src_image_stride, dst_stride, dst_image_stride):
     """aai_resample_batch_multi_device_f32: `shards` is a list of (device, count, src_ptr, dst_ptr, stream) -- one batch of
     independent images spread over several GPUs of this process, no collective."""

@@ -1,5 +1,6 @@
 // aai_adjoint_math.hpp -- per-pixel bodies of the adjoint (transposed) resampling, gsrc = W^T gdst, shared between the HIP
-// kernels (aai_adjoint.hip) and the serial CPU replay of the test-suite (tests/emulation/adjoint_emulation.cpp).
+// kernels (aai_adjoint.hip, aai_adjoint_multi.hip) and the serial CPU replays of the test-suite (tests/emulation/adjoint_emulation.cpp,
+// adjoint_multi_emulation.cpp).
 //
 // W is the matrix aai_resample_device_f32 applies: W[d, s] = weight(d, s) / (sum over s' of weight(d, s')), where weight is
 // the overlap area of dst pixel d with virtual source pixel s (area mode) or the membership of s's centre in d's closed
@@ -10,6 +11,8 @@
 //   1. adjoint_normalised: one dst pixel.  n[d] = gdst[d] / sum of weights (0 where the forward writes 0).
 //   2. adjoint_gather:     one SOURCE pixel.  gsrc[s] = sum over its scale^2 virtual pixels, over the dst pixels d whose
 //                          window (rot_window) holds the virtual pixel, of weight(d, s) n[d].
+// adjoint_normalised_multi / adjoint_gather_multi are the same two passes for C interleaved channels (aai_adjoint_multi.hip,
+// tests/emulation/adjoint_multi_emulation.cpp): the weights do not depend on the channel, so they are computed once per pair.
 //
 // Both evaluate a pair from the same operands as the forward -- (px, py) from pixel_centre(r, dx, dy), ex = X - px -- and the
 // translation units that include this header are compiled without contraction, so a pair gets the same weight whichever
@@ -64,9 +67,9 @@ AAI_HD double adjoint_pair_weight(const RotLaunch &r, int dx, int dy, double px,
     return w;
 }
 
-// pass 1: gd / (sum of the weights of dst pixel (dx, dy)), 0 where the forward writes 0 (Source.cpp:577 / 905)
+// the sum of the weights of dst pixel (dx, dy) over its window, row by row: pass 1's denominator, the same for every channel
 template <int MODE>
-AAI_HD double adjoint_normalised(const RotLaunch &r, int dx, int dy, double gd)
+AAI_HD double adjoint_weight_sum(const RotLaunch &r, int dx, int dy)
 {
     double px, py;
     pixel_centre(r, dx, dy, px, py);
@@ -77,8 +80,30 @@ AAI_HD double adjoint_normalised(const RotLaunch &r, int dx, int dy, double gd)
     double sum = 0.0;
     for (int Y = y0; Y <= y1; ++Y)
         for (int X = x0; X <= x1; ++X) sum += adjoint_pair_weight<MODE>(r, dx, dy, px, py, X, Y, sv4, haveVertices);
-    const bool any = MODE == AAI_MODE_FAST ? sum > 0.0 : DBL_EPSILON < fabs(sum);
+    return sum;
+}
+
+// whether the forward divides by this sum (it writes 0 otherwise: Source.cpp:577 / 905)
+template <int MODE>
+AAI_HD bool adjoint_sum_counts(double sum) { return MODE == AAI_MODE_FAST ? sum > 0.0 : DBL_EPSILON < fabs(sum); }
+
+// pass 1: gd / (sum of the weights of dst pixel (dx, dy)), 0 where the forward writes 0 (Source.cpp:577 / 905)
+template <int MODE>
+AAI_HD double adjoint_normalised(const RotLaunch &r, int dx, int dy, double gd)
+{
+    const double sum = adjoint_weight_sum<MODE>(r, dx, dy);
+    const bool any = adjoint_sum_counts<MODE>(sum);
     return any ? gd / sum : 0.0;
+}
+
+// pass 1 for C interleaved channels: the sum once, then a DIVISION per channel (not a multiplication by the reciprocal), so that
+// channel c gets the bits adjoint_normalised gives plane c
+template <int MODE, int C>
+AAI_HD void adjoint_normalised_multi(const RotLaunch &r, int dx, int dy, const double (&gd)[C], double (&out)[C])
+{
+    const double sum = adjoint_weight_sum<MODE>(r, dx, dy);
+    const bool any = adjoint_sum_counts<MODE>(sum);
+    for (int c = 0; c < C; ++c) out[c] = any ? gd[c] / sum : 0.0;
 }
 
 // How far (in dst pixels, along either dst axis) the centre of a dst pixel can lie from a virtual pixel whose weight is not 0:
@@ -142,6 +167,37 @@ AAI_HD double adjoint_gather(const RotLaunch &r, int sx, int sy, const double *n
                 }
         }
     return acc;
+}
+
+// pass 2 for C interleaved channels: adjoint_gather's enumeration, window test and weight, once per pair; n = pass 1's image of
+// this batch entry with the channels innermost ([dH][dW][C]), so that channel c sums the terms of plane c in plane c's order
+template <int MODE, int C>
+AAI_HD void adjoint_gather_multi(const RotLaunch &r, int sx, int sy, const double *n, double (&acc)[C])
+{
+    const double R = adjoint_reach(r), rL = 1.0 / r.side;
+    for (int c = 0; c < C; ++c) acc[c] = 0.0;
+    for (int jy = 0; jy < r.scale; ++jy)
+        for (int jx = 0; jx < r.scale; ++jx) {
+            int X, Y;
+            adjoint_virtual_pixel(r, sx, sy, jx, jy, X, Y);
+            int dxa, dxb, dya, dyb;
+            if (!adjoint_candidates(r, X, Y, R, rL, dxa, dxb, dya, dyb)) continue;
+            for (int dy = dya; dy <= dyb; ++dy)
+                for (int dx = dxa; dx <= dxb; ++dx) {
+                    double px, py;
+                    pixel_centre(r, dx, dy, px, py);
+                    int x0, x1, y0, y1;
+                    rot_window(r, px, py, x0, x1, y0, y1);
+                    if (X < x0 || X > x1 || Y < y0 || Y > y1) continue;          // the forward does not visit this pair
+                    SVec sv4[4];
+                    bool haveVertices = false;
+                    const double w = adjoint_pair_weight<MODE>(r, dx, dy, px, py, X, Y, sv4, haveVertices);
+                    if (w != 0.0) {
+                        const double *nd = n + ((int64_t)dy * r.dW + dx) * C;
+                        for (int c = 0; c < C; ++c) acc[c] += w * nd[c];
+                    }
+                }
+        }
 }
 
 }  // namespace aai

@@ -19,6 +19,7 @@
 
 #include "aai_engine.hpp"
 #include "../../include/aai_adjoint_planned.h"
+#include "../../include/aai_adjoint_interleaved.h"
 
 using namespace aai::engine;
 
@@ -97,6 +98,19 @@ int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t ds
     AAI_TRY(check_adjoint_request(rq, batch, g));
     AAI_TRY(check_pointers(gdst, gsrc));
     return check_strides(g, 1, srcStride, dstStride);
+}
+
+// the interleaved adjoint: the channel count right after the request (as the forward's interleaved entries report it), then what every
+// adjoint entry checks, then the row length and the strides in elements of `channels` per pixel
+int check_adjoint_interleaved(const aai_request *rq, int batch, int channels, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride,
+                              aai::Geometry &g)
+{
+    AAI_TRY(check_request(rq));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(check_adjoint_request(rq, batch, g));
+    AAI_TRY(check_row_length(g, channels));
+    AAI_TRY(check_pointers(gdst, gsrc));
+    return check_strides(g, channels, srcStride, dstStride);
 }
 
 typedef int (*AdjointEnqueue)(const aai_request &, const aai::Geometry &, int, const float *, int64_t, int64_t, float *, int64_t, int64_t, hipStream_t);
@@ -265,6 +279,24 @@ int adjoint_host(AdjointEnqueue run, const aai_request *req, const float *gdst, 
     AAI_TRY(run(*req, g, 1, dGdst.as<const float>(), g.dW, 0, dGsrc.as<float>(), g.W, 0, stream));
     AAI_HIP(hipStreamSynchronize(stream));
     AAI_HIP(download(gsrc, src_stride, dGsrc, g.W, g.H, sizeof(float)));
+    return finish(*req, g, layout);
+}
+
+// aai_adjoint_interleaved_f32: upload gdst, one launch on the null stream, download gsrc (dense rows of width x channels elements on the device)
+int adjoint_interleaved_host(const aai_request *req, int channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint_interleaved(req, 1, channels, gdst, dst_stride, gsrc, src_stride, g));
+    AAI_TRY(require_device());
+    const int64_t rowDst = (int64_t)g.dW * channels, rowSrc = (int64_t)g.W * channels;
+    DeviceBuffer dGdst, dGsrc;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dGdst.alloc(sizeof(float) * (size_t)rowDst * g.dH));
+    AAI_HIP(dGsrc.alloc(sizeof(float) * (size_t)rowSrc * g.H));
+    AAI_HIP(upload(dGdst, gdst, dst_stride, rowDst, g.dH, sizeof(float)));
+    AAI_TRY(enqueue_adjoint_interleaved(*req, g, 1, channels, dGdst.as<const float>(), rowDst, 0, dGsrc.as<float>(), rowSrc, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    AAI_HIP(download(gsrc, src_stride, dGsrc, rowSrc, g.H, sizeof(float)));
     return finish(*req, g, layout);
 }
 
@@ -468,6 +500,25 @@ int aai_adjoint_planned_batch_device_f32(const aai_request *req, int32_t batch,
 int aai_adjoint_planned_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
 {
     return adjoint_host(enqueue_adjoint_planned, req, gdst, dst_stride, gsrc, src_stride, layout);
+}
+
+int aai_adjoint_interleaved_device_f32(const aai_request *req, int32_t batch, int32_t channels,
+                                       const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                       float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint_interleaved(req, batch, channels, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue_adjoint_interleaved(*req, g, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_adjoint_interleaved_f32(const aai_request *req, int32_t channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride,
+                                aai_layout *layout)
+{
+    return adjoint_interleaved_host(req, channels, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
 int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)

@@ -596,14 +596,15 @@ static int adjoint_scratch_pool(int device, hipMemPool_t *out)
     return AAI_OK;
 }
 
-int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
-                    float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+// the two launches of the general adjoint on `stream`, chunk by chunk; channels == 1: aai_adjoint.hip, 2..4: aai_adjoint_multi.hip
+static int enqueue_adjoint_channels(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
+                                    int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
 {
     // (AAI_POLICY_DOUBLE_PRECISION / AAI_POLICY_PREFER_CELL choose between forward kernels; the adjoint has one, in double precision)
     const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
     const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
-    // scratch: one fp64 image of the dst size per image in flight; large batches go through in chunks of about 1 GiB of it
-    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * sizeof(double);
+    // scratch: one fp64 image of the dst size (times the channels) per image in flight; large batches go through in chunks of about 1 GiB of it
+    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * (size_t)channels * sizeof(double);
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch, kMaxGridZ), ((size_t)1 << 30) / imageBytes));
     int device = 0;
     AAI_HIP(hipGetDevice(&device));
@@ -616,13 +617,31 @@ int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const f
     AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
     const char *name = "";
     hipError_t e = hipSuccess;
-    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk)
-        e = aai::launch_adjoint(r, std::min(batch - b0, chunk), dGdst + (int64_t)b0 * dstImageStride, dv, n, dGsrc + (int64_t)b0 * srcImageStride, sv, stream, &name);
+    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
+        const int nb = std::min(batch - b0, chunk);
+        const float *gd = dGdst + (int64_t)b0 * dstImageStride;
+        float *gs = dGsrc + (int64_t)b0 * srcImageStride;
+        e = channels == 1 ? aai::launch_adjoint(r, nb, gd, dv, n, gs, sv, stream, &name)
+                          : aai::launch_adjoint_multi(r, channels, nb, gd, dv, n, gs, sv, stream, &name);
+    }
     const hipError_t ef = hipFreeAsync(n, stream);
     g_lastKernel = name;
     if (e != hipSuccess) return hip_fail(e, name);
     if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     return AAI_OK;
+}
+
+int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
+                    float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+{
+    return enqueue_adjoint_channels(rq, g, batch, 1, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+}
+
+int enqueue_adjoint_interleaved(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
+                                int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+{
+    if (channels == 1) return enqueue_adjoint(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+    return enqueue_adjoint_channels(rq, g, batch, channels, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
 }
 
 // The adjoint tables of an axis plan (Plan::adjState): the inverse ranges of its two tables and, where it has flagged pixels, the

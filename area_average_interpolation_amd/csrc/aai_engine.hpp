@@ -152,5 +152,12 @@ int enqueue(const aai_request &rq, const Geometry &g, int batch, const void *dSr
 int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
                     float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 
+// The adjoint of images with `channels` = 1..4 interleaved channels (aai_adjoint_interleaved_*; the caller has checked the arguments).
+// One channel: enqueue_adjoint, identical bits.  Otherwise the channel-aware kernels (aai_adjoint_multi.hip) with scratch of
+// dW x dH x channels doubles per image in flight from the same pool, the chunk sized from that; only enqueues, never synchronises.
+// Element (x, y, c) of image b at b * imageStride + y * stride + x * channels + c.
+int enqueue_adjoint_interleaved(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
+                                int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
+
 }  // namespace engine
 }  // namespace aai

@@ -115,6 +115,12 @@ hipError_t launch_cell(const RotLaunch &r, const QuadMap &m, const void *src, in
 hipError_t launch_adjoint(const RotLaunch &r, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
                           hipStream_t stream, const char **kernelName);
 
+// the same two passes for `channels` = 2..4 interleaved channels (aai_adjoint_multi.hip): a pair's weight is computed once for all
+// channels, channel c gets the bits launch_adjoint gives plane c.  gdst / gsrc: element (x, y, c) at y * rowStride + x * channels + c;
+// n = scratch of batch x dH x dW x channels doubles, channels innermost.  `batch` <= 65535.
+hipError_t launch_adjoint_multi(const RotLaunch &r, int channels, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
+                                hipStream_t stream, const char **kernelName);
+
 // the same two passes over LISTS of pixels (the correction pass behind the transposed separable kernel): pass 1 over the nDst dst
 // pixels of dstList into n (the other elements of n are neither written nor read), pass 2 over the nSrc source pixels of srcList,
 // whose gsrc it OVERWRITES.  The lists hold every dst pixel pass 2 reads (build_adjoint_lists).  `batch` <= 65535.

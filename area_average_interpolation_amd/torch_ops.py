@@ -15,15 +15,15 @@ from . import _lib as L
 from . import api
 
 
-def _ensure_prepared(rq):
-    """The forward's first call per (geometry, device) builds a plan and synchronises (aai_prepare): do that now, outside
-    any stream capture.  Inside a capture an unprepared geometry is an error, not a hidden synchronisation."""
-    if api.plan_shape(rq):
+def _ensure_prepared(rq, channels=1):
+    """The forward's first call per (geometry, channel count, device) builds a plan and synchronises (aai_prepare): do that now,
+    outside any stream capture.  Inside a capture an unprepared geometry is an error, not a hidden synchronisation."""
+    if api.plan_shape(rq, channels):
         return
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("resample(): this geometry has no plan on this device yet and the current stream is being captured; "
                            "call resample() (or prepare()) once with the same geometry before capturing")
-    api.prepare(rq)
+    api.prepare(rq, channels)
 
 
 def _ensure_adjoint_prepared(rq):
@@ -70,10 +70,65 @@ class _Resample(torch.autograd.Function):
         return gx, None, None, None
 
 
+class _ResampleInterleaved(torch.autograd.Function):
+    """(B, C, H, W) dense in torch.channels_last, 2 <= C <= 4: the NHWC storage is the library's interleaved layout, nothing is copied"""
+
+    @staticmethod
+    def forward(ctx, x, rq, lay):
+        B, C, H, W = x.shape
+        dH, dW = lay.dst_height, lay.dst_width
+        y = torch.empty((B, C, dH, dW), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        ctx.rq, ctx.src_shape = rq, (B, C, H, W)
+        with torch.cuda.device(x.device):
+            _ensure_prepared(rq, C)
+            api.resample_interleaved_device(rq, C, x.data_ptr(), W * C, y.data_ptr(), dW * C, stream=torch.cuda.current_stream().cuda_stream,
+                                            batch=B, src_image_stride=H * W * C, dst_image_stride=dH * dW * C)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        B, C, H, W = ctx.src_shape
+        if gy.dtype != torch.float32:
+            gy = gy.float()
+        gy = gy.contiguous(memory_format=torch.channels_last)
+        gx = torch.empty((B, C, H, W), dtype=torch.float32, device=gy.device, memory_format=torch.channels_last)
+        dH, dW = gy.shape[2], gy.shape[3]
+        with torch.cuda.device(gy.device):
+            api.adjoint_interleaved_device(ctx.rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, stream=torch.cuda.current_stream().cuda_stream,
+                                           batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C)
+        return gx, None, None
+
+
+def _query(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy):
+    rq = api.make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = api.query(rq)
+    if rc != L.OK:
+        raise api.AaiError(rc, msg)
+    return rq, lay
+
+
+def _resample_nchw(x, geometry, mode, policy, planned):
+    B, C, H, W = x.shape
+    rq, lay = _query(W, H, *geometry, mode, policy)
+    iso = (lay.dst_iso_x, lay.dst_iso_y)
+    if B == 0 or C == 0:
+        return torch.empty((B, C, lay.dst_height, lay.dst_width), dtype=torch.float32, device=x.device), iso
+    if x.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
+        raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
+    interleaved = 2 <= C <= 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
+    if interleaved and planned and lay.kernel == L.KERNEL_AXIS:
+        interleaved = False          # the planned adjoint is single-channel, and far faster there than the interleaved gather
+    if interleaved:
+        return _ResampleInterleaved.apply(x, rq, lay), iso
+    y = _Resample.apply(x.contiguous().view(B * C, H, W), rq, lay, planned)
+    return y.view(B, C, lay.dst_height, lay.dst_width), iso
+
+
 def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
              planned_backward=False):
-    """Resample a CUDA/HIP fp32 tensor of shape (H, W) or (B, H, W); returns ``(y, dst_isocenter)`` with y of shape
-    (dH, dW) or (B, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
+    """Resample a CUDA/HIP fp32 tensor of shape (H, W), (B, H, W) or (B, C, H, W); returns ``(y, dst_isocenter)`` with y of shape
+    (dH, dW), (B, dH, dW) or (B, C, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
     bilinear / bicubic comparison paths have no adjoint: an x that requires grad raises ValueError there).  Non-contiguous
     input is made contiguous; other dtypes raise TypeError, CPU tensors and other ranks ValueError, an invalid geometry
     AaiError.
@@ -83,15 +138,31 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     separable kernel on the forward's own plan (fp32 weights and sums, within a few 1e-7 relative of the default, and one to two
     orders of magnitude faster there), the default's kernels and bits at every other rotation.  With True and an x that requires
     grad the forward also builds the plan's adjoint tables (aai_adjoint_prepare; it synchronises once per geometry and device), so
-    inside a stream capture a geometry without them raises RuntimeError, like a geometry without a plan."""
+    inside a stream capture a geometry without them raises RuntimeError, like a geometry without a plan.
+
+    (B, C, H, W) input takes one of two routes, every plane resampled with the same geometry:
+      planar       x.contiguous() viewed as (B * C, H, W) through the 3-D operator and reshaped back: the 3-D operator's bits plane by
+                   plane, planned_backward honoured.  Every input the interleaved route does not take, channels_last tensors with
+                   C = 1 or C > 4 among them.
+      interleaved  x dense in torch.channels_last (and not dense in the default format) with 2 <= C <= 4: zero-copy on the NHWC
+                   storage.  Forward aai_resample_interleaved_device (the plan prepared for C channels; y is channels_last and within
+                   the library's tolerance of the planar forward, not its bits); backward aai_adjoint_interleaved_device_f32 on a
+                   channels_last gy (x.grad is channels_last; each channel has the bits of the default single-channel adjoint, a
+                   pair's weight computed once for all channels).
+                   EXCEPTION: with planned_backward=True and a geometry the separable kernel serves (aai_query: AAI_KERNEL_AXIS)
+                   the planar route is taken -- the planned adjoint is single-channel and one to two orders of magnitude faster
+                   there than the general gather, which the interleaved adjoint is.
+    B == 0 or C == 0 returns an empty tensor of the output's shape without a launch."""
     if not isinstance(x, torch.Tensor):
         raise TypeError("resample() takes a torch.Tensor")
     if x.dtype != torch.float32:
         raise TypeError("resample() takes a float32 tensor, got %s" % x.dtype)
+    if x.dim() not in (2, 3, 4):
+        raise ValueError("resample() takes a tensor of shape (H, W), (B, H, W) or (B, C, H, W)")
     if not x.is_cuda:
         raise ValueError("resample() takes a tensor on a GPU (the library has no CPU path)")
-    if x.dim() not in (2, 3):
-        raise ValueError("resample() takes a tensor of shape (H, W) or (B, H, W)")
+    if x.dim() == 4:
+        return _resample_nchw(x, (src_resolution, dst_resolution, src_isocenter, rotation_angle), mode, policy, bool(planned_backward))
     xb = (x if x.dim() == 3 else x.unsqueeze(0)).contiguous()
     rq = api.make_request(xb.shape[2], xb.shape[1], src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     rc, msg, lay = api.query(rq)

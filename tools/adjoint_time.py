@@ -8,7 +8,11 @@ device events, forward and adjoint alternating; reported: median, 10th..90th per
 separable kernel), the general adjoint and the planned adjoint (aai_adjoint_planned_batch_device_f32, after aai_adjoint_prepare) --
 with the largest deviation of the planned from the general result relative to max(|general|, 1e-3 max|general|) at the end of each row.
 
-usage: python tools/adjoint_time.py [--planned] [--launches N] [--out FILE]      (the table also goes to stdout)"""
+--channels: the interleaved adjoint (aai_adjoint_interleaved_device_f32) on INTERLEAVED_ROWS with C = 3 and C = 4, two legs taking
+turns -- one interleaved call, and C calls of the unchanged single-channel entry on planes split beforehand (the split is not timed) --
+with the ratio of the medians (interleaved / planar) and whether the two results have the same bits at the end of each row.
+
+usage: python tools/adjoint_time.py [--planned | --channels] [--launches N] [--out FILE]      (the table also goes to stdout)"""
 import argparse
 import os
 import subprocess
@@ -22,6 +26,57 @@ GEOMETRIES = [("cfg3", 8192, 8192, 8192.0, 2731.0, 17.5), ("wide8", 8192, 8192, 
               ("axis4", 4096, 4096, 4.0, 1.0, 0.0), ("quarter2.5", 4096, 4096, 2.5, 1.0, 90.0)]
 # the planned adjoint's rows: the two axis rows above, a flipped quadrant and a transposed up-sampling
 PLANNED_GEOMETRIES = [GEOMETRIES[3], GEOMETRIES[4], ("half180", 4096, 4096, 2.0, 1.0, 180.0), ("up2x270", 2048, 2048, 1.0, 2.0, 270.0)]
+# the interleaved adjoint's rows: (geometry name, mode)
+INTERLEAVED_ROWS = [("cfg3", 1), ("cfg3", 2), ("up2", 1)]
+
+
+def child_channels(name, mode, channels, launches):
+    import numpy as np
+    import torch
+    import area_average_interpolation_amd as aai
+    aai.set_device(0)
+    _, W, H, sr, dr, ang = [g for g in GEOMETRIES if g[0] == name][0]
+    C = channels
+    rq = aai.make_request(W, H, sr, dr, ((W - 1) / 2, (H - 1) / 2), ang, mode=mode)
+    lay = aai.query(rq)[2]
+    dW, dH = lay.dst_width, lay.dst_height
+    st = torch.cuda.current_stream().cuda_stream
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    gd = torch.rand((dH, dW, C), dtype=torch.float32, device="cuda", generator=gen)
+    planes = gd.permute(2, 0, 1).contiguous()                       # split beforehand: not part of either leg
+    gs = torch.empty((H, W, C), dtype=torch.float32, device="cuda")
+    ps = torch.empty((C, H, W), dtype=torch.float32, device="cuda")
+    kernels = {}
+
+    def run_interleaved():
+        aai.adjoint_interleaved_device(rq, C, gd.data_ptr(), dW * C, gs.data_ptr(), W * C, st)
+        kernels["interleaved"] = aai.last_kernel()
+
+    def run_planar():
+        for c in range(C):
+            aai.adjoint_device(rq, planes[c].data_ptr(), dW, ps[c].data_ptr(), W, st)
+        kernels["planar"] = aai.last_kernel()
+
+    runs = {"interleaved": run_interleaved, "planar": run_planar}
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in runs}
+    for _ in range(launches):
+        for key, fn in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[key].append(a.elapsed_time(b))
+    same = torch.equal(gs.permute(2, 0, 1).contiguous().view(torch.int32), ps.view(torch.int32))
+    t = {k: np.array(v) for k, v in times.items()}
+    cell = lambda v: "%8.3f ms (%.3f..%.3f)" % (np.median(v), np.percentile(v, 10), np.percentile(v, 90))
+    print("%-10s %-4s C=%d %5dx%-5d -> %5dx%-5d  interleaved %s  %d planar calls %s  interleaved/planar %5.2f  bits %s  [%s; %s]" % (
+        name, "area" if mode == aai.MODE_AREA else "fast", C, W, H, dW, dH, cell(t["interleaved"]), C, cell(t["planar"]),
+        np.median(t["interleaved"]) / np.median(t["planar"]), "same" if same else "DIFFERENT", kernels["interleaved"], kernels["planar"]), flush=True)
 
 
 def child_planned(name, mode, launches):
@@ -120,12 +175,36 @@ def main():
     ap.add_argument("--launches", type=int, default=24)
     ap.add_argument("--out", default=None)
     ap.add_argument("--planned", action="store_true")
-    ap.add_argument("--child", nargs=2, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--channels", action="store_true")
+    ap.add_argument("--child", nargs="+", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.launches < 20:
         ap.error("at least 20 timed launches")
+    if args.planned and args.channels:
+        ap.error("--planned and --channels are separate tables")
     if args.child:
-        (child_planned if args.planned else child)(args.child[0], int(args.child[1]), args.launches)
+        if args.channels:
+            child_channels(args.child[0], int(args.child[1]), int(args.child[2]), args.launches)
+        else:
+            (child_planned if args.planned else child)(args.child[0], int(args.child[1]), args.launches)
+        return 0
+    if args.channels:
+        lines = ["# median (10th..90th percentile) of %d launches each, device events, the interleaved call and the C single-channel calls "
+                 "on pre-split planes taking turns, one process per row" % args.launches]
+        print(lines[0], flush=True)
+        for name, mode in INTERLEAVED_ROWS:
+            for channels in (3, 4):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--channels", "--launches", str(args.launches),
+                                    "--child", name, str(mode), str(channels)], capture_output=True, text=True, timeout=240)
+                if r.returncode != 0:
+                    sys.stderr.write(r.stdout + r.stderr)
+                    return r.returncode or 1
+                line = [ln for ln in r.stdout.splitlines() if ln.startswith(name)][-1]
+                print(line, flush=True)
+                lines.append(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
         return 0
     lines = ["# median (10th..90th percentile) of %d launches each, device events, %s, one process per row"
              % (args.launches, "forward, general adjoint and planned adjoint taking turns" if args.planned else "forward and adjoint alternating")]

@@ -277,6 +277,19 @@ def resample_device(request, src_ptr, src_stride, dst_ptr, dst_stride, stream=0,
         raise AaiError(rc, last_error())
 
 
+_ADJOINT_DEVICE_ENTRY = {"general": "aai_adjoint_batch_device_f32", "planned": "aai_adjoint_planned_batch_device_f32", "any": "aai_adjoint_rotated_batch_device_f32"}
+_ADJOINT_HOST_ENTRY = {"general": "aai_adjoint_f32", "planned": "aai_adjoint_planned_f32", "any": "aai_adjoint_rotated_f32"}
+
+
+def _planned_kind(planned):
+    """planned=False | True | "any" of adjoint_device / adjoint_host -> which family of entries serves the call"""
+    if isinstance(planned, str):
+        if planned != "any":
+            raise ValueError('planned must be False, True or "any", got %r' % (planned,))
+        return "any"
+    return "planned" if planned else "general"
+
+
 def adjoint_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None,
                    dst_image_stride=0, src_image_stride=0, planned=False):
     """aai_adjoint_batch_device_f32: gsrc = W(request)^T gdst on device-resident fp32 images -- the transpose of what
@@ -284,8 +297,11 @@ def adjoint_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0
     every element of the src_width x src_height gradient image is written.
     planned=True: aai_adjoint_planned_batch_device_f32 -- at rotations by multiples of 90 degrees the transposed separable kernel
     on the forward's cached plan (fp32; the first call of a geometry builds the plan's adjoint tables and synchronises, see
-    adjoint_prepare), the same general kernels for every other request."""
-    fn = L.load().aai_adjoint_planned_batch_device_f32 if planned else L.load().aai_adjoint_batch_device_f32
+    adjoint_prepare), the same general kernels for every other request.
+    planned="any": aai_adjoint_rotated_batch_device_f32 -- one entry for every rotation: what planned=True does at multiples of 90
+    degrees, and at every other rotation the general adjoint's bits from the plan's cached sums and the plain closed forms (the
+    first call of a geometry builds them and synchronises, see adjoint_rotated_prepare)."""
+    fn = getattr(L.load(), _ADJOINT_DEVICE_ENTRY[_planned_kind(planned)])
     rc = fn(_ref(request), 1 if batch is None else int(batch), gdst_ptr, dst_stride, dst_image_stride,
             gsrc_ptr, src_stride, src_image_stride, stream)
     if rc != L.OK:
@@ -300,9 +316,18 @@ def adjoint_prepare(request):
         raise AaiError(rc, last_error())
 
 
+def adjoint_rotated_prepare(request):
+    """aai_adjoint_rotated_prepare: aai_prepare plus the plan's adjoint tables at EVERY rotation -- the sums and knife lists of a general
+    rotation (8 bytes per dst pixel on the device), the tables of adjoint_prepare at multiples of 90 degrees -- so that
+    adjoint_device(..., planned="any") only enqueues."""
+    rc = L.load().aai_adjoint_rotated_prepare(_ref(request))
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
 def adjoint_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle,
                  mode=L.MODE_AREA, policy=L.POLICY_REFERENCE, planned=False):
-    """Host-buffer adjoint (aai_adjoint_f32; planned=True: aai_adjoint_planned_f32): gdst is the [dH, dW] gradient with respect to
+    """Host-buffer adjoint (aai_adjoint_f32; planned=True: aai_adjoint_planned_f32; planned="any": aai_adjoint_rotated_f32): gdst is the [dH, dW] gradient with respect to
     the output of resample_host(src of shape src_shape = (H, W), ...); returns (code, message, gsrc [H, W] float32 or None)."""
     lib = L.load()
     H, W = int(src_shape[0]), int(src_shape[1])
@@ -314,7 +339,7 @@ def adjoint_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter,
     if g.shape != (lay.dst_height, lay.dst_width):
         raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width),))
     gsrc = np.empty((H, W), dtype=np.float32)
-    fn = lib.aai_adjoint_planned_f32 if planned else lib.aai_adjoint_f32
+    fn = getattr(lib, _ADJOINT_HOST_ENTRY[_planned_kind(planned)])
     rc = fn(_ref(rq), g.ctypes.data, max(lay.dst_width, 1), gsrc.ctypes.data, W, None)
     if rc != L.OK:
         return rc, last_error(), None
@@ -393,7 +418,8 @@ def resample_band_device(request, dst_row0, dst_row1, src_rows_ptr, src_stride, 
 
 def plan_shape(request, channels=1):
     """aai_plan_info: one line describing the cached whole-image plan of this request on the current device ("" if none):
-    kernel family, K1 launch shape and its origin, flagged pixels, fp32 formulation, build time, adjoint tables (tables | none)."""
+    kernel family, K1 launch shape and its origin, flagged pixels, fp32 formulation, build time, adjoint tables (tables | none), and last the tables of the planned adjoint at general rotations
+    (rot_adjoint=none | sums | general, then knife=<count> once its scan has run)."""
     buf = ctypes.create_string_buffer(512)
     rc = L.load().aai_plan_info(_ref(request), int(channels), buf, 512)
     if rc != L.OK:

@@ -42,6 +42,23 @@ __global__ __launch_bounds__(kAdjTile *kAdjTile) void aai_adjoint_gather_kernel(
     gsrc[(int64_t)blockIdx.z * sv.imageStride + (int64_t)sy * sv.rowStride + sx] = (float)g;
 }
 
+// The one-off kernel behind the planned adjoint at general rotations (aai_adjoint_plain.hip, aai_adjoint_plain.hpp): pass 1's sum of
+// every dst pixel, kept per plan, a byte that says whether a pair of its window reported a knife edge, and the count of such pixels.
+template <int MODE>
+__global__ __launch_bounds__(kAdjTile *kAdjTile) void aai_adjoint_sums_kernel(RotLaunch r, double *__restrict__ S, unsigned char *__restrict__ knife,
+                                                                                  unsigned *__restrict__ count, int tileRow0)
+{
+    const int dx = blockIdx.x * kAdjTile + threadIdx.x;
+    const int dy = (tileRow0 + blockIdx.y) * kAdjTile + threadIdx.y;
+    if (dx >= r.dW || dy >= r.dH) return;
+    bool k = false;
+    const double sum = adjoint_weight_sum_report<MODE>(r, dx, dy, k);
+    const int64_t i = (int64_t)dy * r.dW + dx;
+    S[i] = sum;
+    knife[i] = k ? 1 : 0;
+    if (k) atomicAdd(count, 1u);
+}
+
 // The two passes over lists of pixels: the per-pixel bodies of the whole-image kernels above, one lane per list entry (x, y).
 constexpr int kAdjListBlock = 256;
 
@@ -76,6 +93,33 @@ hipError_t launch_adjoint_listed(const RotLaunch &r, int batch, const float *gds
     else hipLaunchKernelGGL(aai_adjoint_norm_listed_kernel<AAI_MODE_AREA>, gridD, block, 0, stream, r, gdst, dv, n, dstList, nDst);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (r.mode == AAI_MODE_FAST) hipLaunchKernelGGL(aai_adjoint_gather_listed_kernel<AAI_MODE_FAST>, gridS, block, 0, stream, r, n, gsrc, sv, srcList, nSrc);
+    else hipLaunchKernelGGL(aai_adjoint_gather_listed_kernel<AAI_MODE_AREA>, gridS, block, 0, stream, r, n, gsrc, sv, srcList, nSrc);
+    return hipGetLastError();
+}
+
+// S: dH x dW doubles, knife: dH x dW bytes, count: one zeroed word.  Only enqueues.
+hipError_t launch_adjoint_sums(const RotLaunch &r, double *S, unsigned char *knife, unsigned *count, hipStream_t stream)
+{
+    if (r.dW <= 0 || r.dH <= 0) return hipSuccess;
+    const dim3 block(kAdjTile, kAdjTile, 1);
+    const int tileRows = (r.dH + kAdjTile - 1) / kAdjTile;
+    for (int t0 = 0; t0 < tileRows; t0 += 65535) {            // grid.y carries at most 65535 tiles
+        const dim3 grid((r.dW + kAdjTile - 1) / kAdjTile, tileRows - t0 < 65535 ? tileRows - t0 : 65535, 1);
+        if (r.mode == AAI_MODE_FAST) hipLaunchKernelGGL(aai_adjoint_sums_kernel<AAI_MODE_FAST>, grid, block, 0, stream, r, S, knife, count, t0);
+        else hipLaunchKernelGGL(aai_adjoint_sums_kernel<AAI_MODE_AREA>, grid, block, 0, stream, r, S, knife, count, t0);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// the listed gather alone: n is complete already (the planned adjoint at general rotations, whose pass 1 is element-wise)
+hipError_t launch_adjoint_gather_listed(const RotLaunch &r, int batch, const double *n, float *gsrc, ImageView sv, const uint2 *srcList, unsigned nSrc,
+                                        hipStream_t stream)
+{
+    if (batch <= 0 || !nSrc) return hipSuccess;
+    const dim3 block(kAdjListBlock, 1, 1), gridS((nSrc + kAdjListBlock - 1) / kAdjListBlock, 1, batch);
     if (r.mode == AAI_MODE_FAST) hipLaunchKernelGGL(aai_adjoint_gather_listed_kernel<AAI_MODE_FAST>, gridS, block, 0, stream, r, n, gsrc, sv, srcList, nSrc);
     else hipLaunchKernelGGL(aai_adjoint_gather_listed_kernel<AAI_MODE_AREA>, gridS, block, 0, stream, r, n, gsrc, sv, srcList, nSrc);
     return hipGetLastError();

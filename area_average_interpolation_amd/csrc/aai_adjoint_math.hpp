@@ -1,6 +1,6 @@
 // aai_adjoint_math.hpp -- per-pixel bodies of the adjoint (transposed) resampling, gsrc = W^T gdst, shared between the HIP
 // kernels (aai_adjoint.hip, aai_adjoint_multi.hip) and the serial CPU replays of the test-suite (tests/emulation/adjoint_emulation.cpp,
-// adjoint_multi_emulation.cpp).
+// adjoint_multi_emulation.cpp).  aai_adjoint_plain.hpp builds the planned adjoint at general rotations on the *_report forms below.
 //
 // W is the matrix aai_resample_device_f32 applies: W[d, s] = weight(d, s) / (sum over s' of weight(d, s')), where weight is
 // the overlap area of dst pixel d with virtual source pixel s (area mode) or the membership of s's centre in d's closed
@@ -34,8 +34,10 @@ namespace aai {
 
 // weight of the pair (dst pixel (dx, dy) centred at (px, py), virtual pixel (X, Y)) -- the per-pair code of the forward's
 // fix-up pass.  sv4 / haveVertices: the reference's vertices of the dst pixel, fetched on the first knife edge.
+// knife: set (never cleared) when the pair reported a knife edge -- edgy / edgy2, i.e. when the strict replay decided its weight.  A pair
+// that leaves it alone got the weight of the plain closed forms (adjoint_plain_pair_weight in aai_adjoint_plain.hpp), bit for bit.
 template <int MODE>
-AAI_HD double adjoint_pair_weight(const RotLaunch &r, int dx, int dy, double px, double py, int X, int Y, SVec sv4[4], bool &haveVertices)
+AAI_HD double adjoint_pair_weight_report(const RotLaunch &r, int dx, int dy, double px, double py, int X, int Y, SVec sv4[4], bool &haveVertices, bool &knife)
 {
     const double ex = X - px, ey = Y - py;
     if (MODE == AAI_MODE_FAST) {
@@ -45,6 +47,7 @@ AAI_HD double adjoint_pair_weight(const RotLaunch &r, int dx, int dy, double px,
         bool in = a <= lim && b <= lim;
         const bool edgy = (fabs(a - r.h) < AAI_KNIFE_GUARD && b <= r.h + AAI_KNIFE_GUARD) || (fabs(b - r.h) < AAI_KNIFE_GUARD && a <= r.h + AAI_KNIFE_GUARD);
         if (edgy) {                      // a centre on an edge: the reference's ray cast decides
+            knife = true;
             if (!haveVertices) { strict_vertices(r, dx, dy, sv4); haveVertices = true; }
             SVec pc; pc.x = X; pc.y = Y;
             in = strict_centre_inside(pc, sv4);
@@ -60,6 +63,7 @@ AAI_HD double adjoint_pair_weight(const RotLaunch &r, int dx, int dy, double px,
         else if (cls == PAIR_GENERAL) w = wedge_pair_area<true>(r, px - (X - 0.5), py - (Y - 0.5), a < 0.0, b < 0.0, r.policy, edgy2);
         else w = single_cut_area<true>(r, d, cls == PAIR_CUT_LR, r.policy, edgy2);
         if (edgy || edgy2) {
+            knife = true;
             if (!haveVertices) { strict_vertices(r, dx, dy, sv4); haveVertices = true; }
             w = strict_pair_area(sv4, X, Y, r.policy);
         }
@@ -67,9 +71,17 @@ AAI_HD double adjoint_pair_weight(const RotLaunch &r, int dx, int dy, double px,
     return w;
 }
 
-// the sum of the weights of dst pixel (dx, dy) over its window, row by row: pass 1's denominator, the same for every channel
 template <int MODE>
-AAI_HD double adjoint_weight_sum(const RotLaunch &r, int dx, int dy)
+AAI_HD double adjoint_pair_weight(const RotLaunch &r, int dx, int dy, double px, double py, int X, int Y, SVec sv4[4], bool &haveVertices)
+{
+    bool knife = false;
+    return adjoint_pair_weight_report<MODE>(r, dx, dy, px, py, X, Y, sv4, haveVertices, knife);
+}
+
+// the sum of the weights of dst pixel (dx, dy) over its window, row by row: pass 1's denominator, the same for every channel
+// (knife: whether any pair of the window reported a knife edge -- the per-plan table of the rotated planned adjoint lists these pixels)
+template <int MODE>
+AAI_HD double adjoint_weight_sum_report(const RotLaunch &r, int dx, int dy, bool &knife)
 {
     double px, py;
     pixel_centre(r, dx, dy, px, py);
@@ -79,8 +91,14 @@ AAI_HD double adjoint_weight_sum(const RotLaunch &r, int dx, int dy)
     bool haveVertices = false;
     double sum = 0.0;
     for (int Y = y0; Y <= y1; ++Y)
-        for (int X = x0; X <= x1; ++X) sum += adjoint_pair_weight<MODE>(r, dx, dy, px, py, X, Y, sv4, haveVertices);
+        for (int X = x0; X <= x1; ++X) sum += adjoint_pair_weight_report<MODE>(r, dx, dy, px, py, X, Y, sv4, haveVertices, knife);
     return sum;
+}
+template <int MODE>
+AAI_HD double adjoint_weight_sum(const RotLaunch &r, int dx, int dy)
+{
+    bool knife = false;
+    return adjoint_weight_sum_report<MODE>(r, dx, dy, knife);
 }
 
 // whether the forward divides by this sum (it writes 0 otherwise: Source.cpp:577 / 905)

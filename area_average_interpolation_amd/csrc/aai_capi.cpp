@@ -20,6 +20,7 @@
 #include "aai_engine.hpp"
 #include "../../include/aai_adjoint_planned.h"
 #include "../../include/aai_adjoint_interleaved.h"
+#include "../../include/aai_adjoint_rotated.h"
 
 using namespace aai::engine;
 
@@ -115,7 +116,7 @@ int check_adjoint_interleaved(const aai_request *rq, int batch, int channels, co
 
 typedef int (*AdjointEnqueue)(const aai_request &, const aai::Geometry &, int, const float *, int64_t, int64_t, float *, int64_t, int64_t, hipStream_t);
 
-// aai_adjoint_batch_device_f32 / aai_adjoint_planned_batch_device_f32
+// aai_adjoint_batch_device_f32 / aai_adjoint_planned_batch_device_f32 / aai_adjoint_rotated_batch_device_f32
 int adjoint_device(AdjointEnqueue run, const aai_request *req, int32_t batch, const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
                    float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
@@ -265,7 +266,7 @@ bool is_page_locked(const void *p)
     return attr.type == hipMemoryTypeHost;
 }
 
-// aai_adjoint_f32 / aai_adjoint_planned_f32: upload gdst, one launch on the null stream, download gsrc
+// aai_adjoint_f32 / aai_adjoint_planned_f32 / aai_adjoint_rotated_f32: upload gdst, one launch on the null stream, download gsrc
 int adjoint_host(AdjointEnqueue run, const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
 {
     aai::Geometry g;
@@ -500,6 +501,28 @@ int aai_adjoint_planned_batch_device_f32(const aai_request *req, int32_t batch,
 int aai_adjoint_planned_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
 {
     return adjoint_host(enqueue_adjoint_planned, req, gdst, dst_stride, gsrc, src_stride, layout);
+}
+
+int aai_adjoint_rotated_prepare(const aai_request *req)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint_request(req, 1, g));
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue_adjoint_rotated(*req, g, 0, nullptr, 0, 0, nullptr, 0, 0, nullptr));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_adjoint_rotated_batch_device_f32(const aai_request *req, int32_t batch,
+                                         const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                         float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    return adjoint_device(enqueue_adjoint_rotated, req, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
+}
+
+int aai_adjoint_rotated_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
+{
+    return adjoint_host(enqueue_adjoint_rotated, req, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
 int aai_adjoint_interleaved_device_f32(const aai_request *req, int32_t batch, int32_t channels,

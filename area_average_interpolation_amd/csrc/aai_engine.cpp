@@ -114,6 +114,13 @@ void drop_plans()
 constexpr size_t kMaxPlans = 32;       // per device
 constexpr unsigned kMaxListedPixels = 1u << 24;      // beyond 16 M flagged pixels the whole image takes the double-precision pass
 
+// (AAI_MAX_LISTED_PIXELS: test hook, lowers the threshold so that small geometries exercise the dense form; documented in include/aai.h)
+static unsigned max_listed_pixels()
+{
+    static const unsigned maxListed = [] { const char *v = getenv("AAI_MAX_LISTED_PIXELS"); return v ? (unsigned)strtoul(v, nullptr, 10) : kMaxListedPixels; }();
+    return maxListed;
+}
+
 bool same_request(const aai_request &a, const aai_request &b)
 {
     // (AAI_POLICY_DIAG_NO_FIXUP is a property of a launch, not of the plan: with and without it a request shares one plan)
@@ -337,8 +344,7 @@ static int build_plan(Plan &p, hipStream_t bs)
     const bool verifyAxis = axisKernel && axis_band_margin(rq) != 0;
     if (p.kernel == AAI_KERNEL_ROTATED || p.kernel == AAI_KERNEL_FAST || verifyAxis) {
         const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
-        // (AAI_MAX_LISTED_PIXELS: test hook, lowers the threshold so that small geometries exercise the dense form)
-        static const unsigned maxListed = [] { const char *v = getenv("AAI_MAX_LISTED_PIXELS"); return v ? (unsigned)strtoul(v, nullptr, 10) : kMaxListedPixels; }();      // documented in include/aai.h
+        const unsigned maxListed = max_listed_pixels();
         std::vector<std::pair<int, int>> hostPixels;
         bool hostDense = false;
         if (verifyAxis && aai::axis_verify_by_class(r, hostPixels, hostDense, maxListed)) {
@@ -489,11 +495,13 @@ std::string plan_description(const aai_request &rq, int channels)
         const Plan &p = *q;
         const bool rotated = p.kernel != AAI_KERNEL_AXIS && p.kernel != AAI_KERNEL_AXIS_WIDE;
         if (p.device == dev && p.band0 < 0 && (rotated || p.channels == channels) && p.built && same_request(p.key, rq)) {
-            char buf[256];
-            // (swap=0: the grid-order field stays in the format that bench.py, the tests and the recorded profiles read)
-            snprintf(buf, sizeof buf, "kernel=%d rows=%d nt=%d swap=0 tune=%s flagged=%u dense=%d form=%s build_ms=%.3f adjoint=%s", p.kernel, p.tuneRows, p.tuneNt,
+            char buf[320];
+            // (swap=0: the grid-order field stays in the format that bench.py, the tests and the recorded profiles read; new tokens go at the end)
+            int len = snprintf(buf, sizeof buf, "kernel=%d rows=%d nt=%d swap=0 tune=%s flagged=%u dense=%d form=%s build_ms=%.3f adjoint=%s rot_adjoint=%s", p.kernel, p.tuneRows, p.tuneNt,
                      p.tuneSource == 1 ? "measured" : (p.tuneSource == 2 ? "cached" : "default"), p.flaggedPixels, p.dense ? 1 : 0,
-                     p.kernel == AAI_KERNEL_ROTATED ? (p.form == aai::ROT_FORM_CELL ? "cell" : "quad") : "-", p.buildMs, p.adjState == 1 ? "tables" : "none");
+                     p.kernel == AAI_KERNEL_ROTATED ? (p.form == aai::ROT_FORM_CELL ? "cell" : "quad") : "-", p.buildMs, p.adjState == 1 ? "tables" : "none",
+                     p.rotAdjState == 1 ? "sums" : (p.rotAdjState == 2 ? "general" : "none"));
+            if (p.adjKnife >= 0 && len > 0 && len < (int)sizeof buf) snprintf(buf + len, sizeof buf - (size_t)len, " knife=%lld", p.adjKnife);
             return std::string(buf);
         }
     }
@@ -747,6 +755,129 @@ int enqueue_adjoint_planned(const aai_request &rq, const Geometry &g, int batch,
     }
     const hipError_t ef = n ? hipFreeAsync(n, stream) : hipSuccess;
     if (e != hipSuccess) return hip_fail(e, "aai_axis_adjoint_kernel");
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    return AAI_OK;
+}
+
+// The tables of the planned adjoint at general rotations (Plan::rotAdjState): the sums of every dst pixel, the dst pixels with a knife-edge
+// pair and, from those, the source pixels the general gather recomputes.  Under p.build; blocks (the one-off kernels on the device
+// pool's build stream, the knife list read back, the source list uploaded).
+static int build_rot_adjoint_tables(Plan &p)
+{
+    if (p.rotAdjState) return AAI_OK;
+    const aai::Geometry &g = p.g;
+    const size_t pixels = (size_t)g.dW * (size_t)g.dH;
+    if ((p.kernel != AAI_KERNEL_ROTATED && p.kernel != AAI_KERNEL_FAST) || p.channels != 1 || p.band0 >= 0 || !pixels ||
+        pixels * sizeof(double) > ((size_t)1 << 30)) {
+        p.rotAdjState = 2;
+        return AAI_OK;
+    }
+    const aai::RotLaunch r = aai::make_rot_launch(g, p.key.mode, p.key.policy);
+    hipStream_t bs = nullptr;
+    AAI_HIP(pool_build_stream(device_pool(p.device), &bs));
+    // ONE scratch allocation: a byte per dst pixel | the count of flagged pixels | the list's cursor
+    const size_t flagBytes = (pixels + 15) & ~(size_t)15;
+    double *dSums = nullptr;
+    char *block = nullptr;
+    void *dKnife = nullptr, *dSrc = nullptr;
+    std::vector<uint2> knife, src2;                                  // (declared before the first copy: alive until the stream is synchronised)
+    unsigned count = 0;
+    bool general = false;
+    hipError_t e = hipMalloc((void **)&dSums, pixels * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&block, flagBytes + 16);
+    unsigned *dCount = reinterpret_cast<unsigned *>(block + flagBytes), *dCursor = dCount + 1;
+    if (e == hipSuccess) e = hipMemsetAsync(dCount, 0, 16, bs);
+    if (e == hipSuccess) e = aai::launch_adjoint_sums(r, dSums, reinterpret_cast<unsigned char *>(block), dCount, bs);
+    if (e == hipSuccess) e = hipMemcpyAsync(&count, dCount, sizeof(unsigned), hipMemcpyDeviceToHost, bs);
+    if (e == hipSuccess) e = hipStreamSynchronize(bs);
+    if (e == hipSuccess && count > max_listed_pixels()) general = true;
+    if (e == hipSuccess && count && !general) {
+        knife.resize(count);
+        e = hipMalloc(&dKnife, (size_t)count * sizeof(uint2));
+        if (e == hipSuccess) e = aai::launch_adjoint_knife_list(r, reinterpret_cast<const unsigned char *>(block), static_cast<uint2 *>(dKnife), dCursor, count, bs);
+        if (e == hipSuccess) e = hipMemcpyAsync(knife.data(), dKnife, (size_t)count * sizeof(uint2), hipMemcpyDeviceToHost, bs);
+        if (e == hipSuccess) e = hipStreamSynchronize(bs);
+        if (e == hipSuccess) {
+            std::vector<std::pair<int, int>> flagged(knife.size()), srcList, dstList;
+            for (size_t i = 0; i < knife.size(); ++i) flagged[i] = std::make_pair((int)knife[i].x, (int)knife[i].y);
+            // (a correction pass over more than half of the source image is the general adjoint with a detour; n is complete here, so
+            // the list of dst pixels is not needed)
+            if (!aai::build_adjoint_lists(r, flagged, std::vector<int>(), std::vector<int>(), (size_t)g.W * g.H / 2, srcList, dstList)) general = true;
+            else {
+                src2.resize(srcList.size());
+                for (size_t i = 0; i < srcList.size(); ++i) src2[i] = make_uint2((unsigned)srcList[i].first, (unsigned)srcList[i].second);
+                if (!src2.empty()) {
+                    e = hipMalloc(&dSrc, src2.size() * sizeof(uint2));
+                    if (e == hipSuccess) e = hipMemcpyAsync(dSrc, src2.data(), src2.size() * sizeof(uint2), hipMemcpyHostToDevice, bs);
+                }
+            }
+        }
+    }
+    const hipError_t es = hipStreamSynchronize(bs);
+    if (e == hipSuccess) e = es;
+    if (block) (void)hipFree(block);
+    if (dKnife) (void)hipFree(dKnife);
+    if (e != hipSuccess || general) {
+        if (dSums) (void)hipFree(dSums);
+        if (dSrc) (void)hipFree(dSrc);
+        if (e != hipSuccess) return hip_fail(e, "building the rotated adjoint tables");      // (rotAdjState stays 0: a later call tries again)
+        p.adjKnife = (long long)count;
+        p.rotAdjState = 2;
+        return AAI_OK;
+    }
+    p.dAdjSums = dSums;
+    p.dAdjSrcList = dSrc; p.adjSrcCount = (unsigned)src2.size();
+    p.adjKnife = (long long)count;
+    p.rotAdjState = 1;
+    return AAI_OK;
+}
+
+int enqueue_adjoint_rotated(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
+                            float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+{
+    const int kernel = pick_kernel(rq, g);
+    if (kernel != AAI_KERNEL_ROTATED && kernel != AAI_KERNEL_FAST)      // reduced angle 0: one entry serves every rotation
+        return enqueue_adjoint_planned(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+    const bool prepareOnly = dGdst == nullptr;
+    PlanRef p;
+    {
+        // the forward's plan under the forward's key (a packed fp32 image, one channel, the whole image)
+        const int rc = acquire_plan(rq, g, -1, -1, 1, rot_form(rq, g, 1, aai::SRC_F32, g.W), &p, /*onCallerStream*/ !prepareOnly, stream);
+        if (rc != AAI_OK) return rc;
+        std::lock_guard<std::mutex> lock(p->build);
+        const int rt = build_rot_adjoint_tables(*p);
+        if (rt != AAI_OK) return rt;
+    }
+    if (prepareOnly) return AAI_OK;
+    if (p->rotAdjState != 1) return enqueue_adjoint(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+
+    std::lock_guard<std::mutex> lock(p->launch);
+    const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
+    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
+    // scratch: one fp64 image of the dst size per image in flight, chunked as in enqueue_adjoint
+    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * sizeof(double);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch, kMaxGridZ), ((size_t)1 << 30) / imageBytes));
+    hipMemPool_t scratch = nullptr;
+    {
+        const int rc = adjoint_scratch_pool(p->device, &scratch);
+        if (rc != AAI_OK) return rc;
+    }
+    double *n = nullptr;
+    AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
+    const char *name = "";
+    const bool listed = p->adjSrcCount != 0;
+    hipError_t e = hipSuccess;
+    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
+        const int nb = std::min(batch - b0, chunk);
+        const float *gd = dGdst + (int64_t)b0 * dstImageStride;
+        float *gs = dGsrc + (int64_t)b0 * srcImageStride;
+        e = aai::launch_adjoint_plain(r, nb, gd, dv, p->dAdjSums, n, gs, sv, stream, &name);
+        if (e == hipSuccess && listed)
+            e = aai::launch_adjoint_gather_listed(r, nb, n, gs, sv, static_cast<const uint2 *>(p->dAdjSrcList), p->adjSrcCount, stream);
+    }
+    const hipError_t ef = hipFreeAsync(n, stream);
+    g_lastKernel = listed ? std::string(name) + "+listed" : std::string(name);
+    if (e != hipSuccess) return hip_fail(e, name);
     if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     return AAI_OK;
 }

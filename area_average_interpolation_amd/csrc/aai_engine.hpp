@@ -61,6 +61,13 @@ struct Plan {
     aai::AxisRange *dColRange = nullptr, *dRowRange = nullptr;
     void *dAdjSrcList = nullptr, *dAdjDstList = nullptr;      // uint2 (x, y): the source pixels the general adjoint recomputes, the dst pixels it reads
     unsigned adjSrcCount = 0, adjDstCount = 0;
+    // the planned adjoint at general rotations (aai_adjoint_rotated_*; rotated area / fast plans): built by its first call of the plan or by
+    // aai_adjoint_rotated_prepare, under `build`.  rotAdjState: 0 = not asked for yet, 1 = sums on the device, 2 = this plan keeps the
+    // general adjoint (too many knife pixels, a source list over more than half of the image, sums beyond 1 GiB).  The source pixels the
+    // general gather recomputes are dAdjSrcList / adjSrcCount above (an axis plan never holds these tables, a rotated plan never those).
+    int rotAdjState = 0;
+    double *dAdjSums = nullptr;      // fp64 [dH][dW]: 8 bytes per dst pixel
+    long long adjKnife = -1;         // dst pixels with a knife-edge pair (-1: not counted)
     double buildMs = 0.0;            // wall clock of build_plan (tables, scans, launch-shape measurement)
     // Built once, by whoever gets here first, under `build` -- NOT under the cache's lock: other requests, other devices
     // and other threads are not held up by this plan's scans or launch-shape measurement.  `launch` serialises the launches of a
@@ -81,6 +88,7 @@ struct Plan {
         if (dRowRange) (void)hipFree(dRowRange);
         if (dAdjSrcList) (void)hipFree(dAdjSrcList);
         if (dAdjDstList) (void)hipFree(dAdjDstList);
+        if (dAdjSums) (void)hipFree(dAdjSums);
     }
 };
 typedef std::shared_ptr<Plan> PlanRef;
@@ -131,12 +139,21 @@ int require_device();
 int enqueue_adjoint_planned(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
                             float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 
+// The planned adjoint at every rotation (aai_adjoint_rotated_*; the caller has checked the arguments).  Reduced angle 0:
+// enqueue_adjoint_planned.  Otherwise the forward's plan (looked up with the forward's key, built like aai_prepare(req, 1) builds it when
+// missing) with its sums and knife lists (built on first need: blocks), then the element-wise pass 1, the plain gather and, where the
+// plan lists source pixels, the listed gather of the general adjoint behind it.  A plan in rotAdjState 2: enqueue_adjoint.
+// dGdst == NULL: prepare only (aai_adjoint_rotated_prepare).
+int enqueue_adjoint_rotated(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
+                            float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
+
 // Finds the plan for (request, current device) or inserts a fresh one, then builds it if nobody has (blocking: table
 // uploads, the one-off scans, K1's launch-shape measurement -- on `stream` when the caller has one to give (onCallerStream; a
 // stream that is being captured into a graph is not used), else on the device pool's build stream).
 // form: aai::RotForm of a rotated request's launch (rot_form below); ignored by the other kernels
 int acquire_plan(const aai_request &rq, const Geometry &g, int band0, int band1, int channels, int form, PlanRef *out, bool onCallerStream = false, hipStream_t stream = nullptr);
-// "kernel=K rows=R nt=N swap=0 tune=T flagged=F dense=D form=M build_ms=B adjoint=tables|none" of the cached whole-image plan ("" when there is none)
+// "kernel=K rows=R nt=N swap=0 tune=T flagged=F dense=D form=M build_ms=B adjoint=tables|none rot_adjoint=none|sums|general[ knife=N]" of the
+// cached whole-image plan ("" when there is none); new tokens are appended at the end
 std::string plan_description(const aai_request &rq, int channels);
 // which fp32 formulation serves a launch of this request: the cell formulation takes plain images below 4 GiB in area mode
 int rot_form(const aai_request &rq, const Geometry &g, int channels, int srcType, int64_t srcStride);

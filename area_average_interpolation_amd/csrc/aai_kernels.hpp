@@ -126,6 +126,20 @@ hipError_t launch_adjoint_multi(const RotLaunch &r, int channels, int batch, con
 // whose gsrc it OVERWRITES.  The lists hold every dst pixel pass 2 reads (build_adjoint_lists).  `batch` <= 65535.
 hipError_t launch_adjoint_listed(const RotLaunch &r, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
                                  const uint2 *dstList, unsigned nDst, const uint2 *srcList, unsigned nSrc, hipStream_t stream);
+// pass 2 of the above alone, over an n that is complete already (behind launch_adjoint_plain)
+hipError_t launch_adjoint_gather_listed(const RotLaunch &r, int batch, const double *n, float *gsrc, ImageView sv, const uint2 *srcList, unsigned nSrc,
+                                        hipStream_t stream);
+
+// ---- the adjoint at general rotations from per-plan sums (aai_adjoint_plain.hip, the one-off sums kernel in aai_adjoint.hip; bodies and the bit-equality argument in
+// aai_adjoint_plain.hpp).  Once per geometry: S[d] = the general normaliser's sum (dH x dW doubles), knife[d] = whether a pair of d's
+// window reported a knife edge (dH x dW bytes), *count += the number of such pixels; then the flagged pixels as a list through *cursor
+// (both words zeroed by the caller; entries beyond `capacity` are dropped).  Only enqueue.
+hipError_t launch_adjoint_sums(const RotLaunch &r, double *S, unsigned char *knife, unsigned *count, hipStream_t stream);
+hipError_t launch_adjoint_knife_list(const RotLaunch &r, const unsigned char *knife, uint2 *list, unsigned *cursor, unsigned capacity, hipStream_t stream);
+// per call: n[b][d] = gdst[b][d] / S[d] (element-wise), then the plain gather over every source pixel, which writes all of gsrc.
+// `batch` <= 65535; n holds batch x dH x dW doubles.  Only enqueues.
+hipError_t launch_adjoint_plain(const RotLaunch &r, int batch, const float *gdst, ImageView dv, const double *S, double *n, float *gsrc, ImageView sv,
+                                hipStream_t stream, const char **kernelName);
 
 // ---- the transpose of K1 (aai_axis_adjoint.hip): the adjoint at rotations by multiples of 90 degrees, fp32, from the forward's tables
 struct AxisAdjointLaunch {

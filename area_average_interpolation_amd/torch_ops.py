@@ -3,7 +3,7 @@
 ``resample(x, ...)`` runs the library's forward (aai_resample_batch_device_f32) on a device-resident fp32 tensor and is a
 ``torch.autograd.Function``: its backward is the library's adjoint (aai_adjoint_batch_device_f32), gsrc = W^T gdst with the
 forward's own weights -- not an approximation through ``grid_sample`` (``planned_backward=True``: the planned adjoint,
-aai_adjoint_planned_batch_device_f32).  Both launch on ``torch.cuda.current_stream()`` of the
+aai_adjoint_planned_batch_device_f32; ``"any"``: aai_adjoint_rotated_batch_device_f32, planned at every rotation).  Both launch on ``torch.cuda.current_stream()`` of the
 tensor's device and only enqueue work.
 
 torch is imported here, not by the package: ``import area_average_interpolation_amd`` works without it.
@@ -39,6 +39,26 @@ def _ensure_adjoint_prepared(rq):
     api.adjoint_prepare(rq)
 
 
+def _ensure_rotated_adjoint_prepared(rq):
+    """planned_backward="any" at a general rotation: the first call of aai_adjoint_rotated_batch_device_f32 per (geometry, device) builds
+    the plan's sums and knife lists and synchronises (aai_adjoint_rotated_prepare): do that in the forward, outside any stream capture."""
+    if "rot_adjoint=none" not in api.plan_shape(rq).split():
+        return
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('resample(planned_backward="any"): this geometry has no adjoint tables on this device yet and the current '
+                           "stream is being captured; call resample() (or adjoint_rotated_prepare()) once with the same geometry before capturing")
+    api.adjoint_rotated_prepare(rq)
+
+
+def _normalise_planned(planned_backward):
+    """False | True | "any" (anything else that is a string raises)"""
+    if isinstance(planned_backward, str):
+        if planned_backward != "any":
+            raise ValueError('planned_backward must be False, True or "any", got %r' % (planned_backward,))
+        return "any"
+    return bool(planned_backward)
+
+
 class _Resample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rq, lay, planned):
@@ -49,7 +69,10 @@ class _Resample(torch.autograd.Function):
             with torch.cuda.device(x.device):
                 _ensure_prepared(rq)
                 if planned and ctx.needs_input_grad[0]:
-                    _ensure_adjoint_prepared(rq)
+                    if planned == "any" and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST):
+                        _ensure_rotated_adjoint_prepared(rq)
+                    else:
+                        _ensure_adjoint_prepared(rq)
                 api.resample_device(rq, x.data_ptr(), W, y.data_ptr(), lay.dst_width, stream=torch.cuda.current_stream().cuda_stream,
                                     batch=B, src_image_stride=H * W, dst_image_stride=lay.dst_height * lay.dst_width)
         return y
@@ -119,6 +142,8 @@ def _resample_nchw(x, geometry, mode, policy, planned):
     interleaved = 2 <= C <= 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
     if interleaved and planned and lay.kernel == L.KERNEL_AXIS:
         interleaved = False          # the planned adjoint is single-channel, and far faster there than the interleaved gather
+    if interleaved and planned == "any" and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST):
+        interleaved = False          # ... and so is the planned adjoint at general rotations
     if interleaved:
         return _ResampleInterleaved.apply(x, rq, lay), iso
     y = _Resample.apply(x.contiguous().view(B * C, H, W), rq, lay, planned)
@@ -138,7 +163,10 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     separable kernel on the forward's own plan (fp32 weights and sums, within a few 1e-7 relative of the default, and one to two
     orders of magnitude faster there), the default's kernels and bits at every other rotation.  With True and an x that requires
     grad the forward also builds the plan's adjoint tables (aai_adjoint_prepare; it synchronises once per geometry and device), so
-    inside a stream capture a geometry without them raises RuntimeError, like a geometry without a plan.
+    inside a stream capture a geometry without them raises RuntimeError, like a geometry without a plan.  "any" -- the backward is
+    aai_adjoint_rotated_batch_device_f32: exactly True at multiples of 90 degrees; at every other rotation the default's BITS from the
+    plan's cached sums (8 bytes per dst pixel on the device) and the plain closed forms, and with an x that requires grad the forward
+    builds those tables (aai_adjoint_rotated_prepare; the same rule inside a stream capture).
 
     (B, C, H, W) input takes one of two routes, every plane resampled with the same geometry:
       planar       x.contiguous() viewed as (B * C, H, W) through the 3-D operator and reshaped back: the 3-D operator's bits plane by
@@ -151,7 +179,8 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
                    pair's weight computed once for all channels).
                    EXCEPTION: with planned_backward=True and a geometry the separable kernel serves (aai_query: AAI_KERNEL_AXIS)
                    the planar route is taken -- the planned adjoint is single-channel and one to two orders of magnitude faster
-                   there than the general gather, which the interleaved adjoint is.
+                   there than the general gather, which the interleaved adjoint is.  The same holds for planned_backward="any" at
+                   every geometry its single-channel path serves (the separable kernel's, and the rotated area / fast kernels').
     B == 0 or C == 0 returns an empty tensor of the output's shape without a launch."""
     if not isinstance(x, torch.Tensor):
         raise TypeError("resample() takes a torch.Tensor")
@@ -162,7 +191,7 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     if not x.is_cuda:
         raise ValueError("resample() takes a tensor on a GPU (the library has no CPU path)")
     if x.dim() == 4:
-        return _resample_nchw(x, (src_resolution, dst_resolution, src_isocenter, rotation_angle), mode, policy, bool(planned_backward))
+        return _resample_nchw(x, (src_resolution, dst_resolution, src_isocenter, rotation_angle), mode, policy, _normalise_planned(planned_backward))
     xb = (x if x.dim() == 3 else x.unsqueeze(0)).contiguous()
     rq = api.make_request(xb.shape[2], xb.shape[1], src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     rc, msg, lay = api.query(rq)
@@ -170,5 +199,5 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         raise api.AaiError(rc, msg)
     if xb.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
         raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
-    y = _Resample.apply(xb, rq, lay, bool(planned_backward))
+    y = _Resample.apply(xb, rq, lay, _normalise_planned(planned_backward))
     return (y if x.dim() == 3 else y.squeeze(0)), (lay.dst_iso_x, lay.dst_iso_y)

@@ -12,7 +12,12 @@ with the largest deviation of the planned from the general result relative to ma
 turns -- one interleaved call, and C calls of the unchanged single-channel entry on planes split beforehand (the split is not timed) --
 with the ratio of the medians (interleaved / planar) and whether the two results have the same bits at the end of each row.
 
-usage: python tools/adjoint_time.py [--planned | --channels] [--launches N] [--out FILE]      (the table also goes to stdout)"""
+--rotated: the planned adjoint at general rotations (aai_adjoint_rotated_batch_device_f32, after aai_adjoint_rotated_prepare) against the
+unchanged general entry on ROTATED_GEOMETRIES -- the general-angle rows of the first table -- both modes, the two legs taking turns;
+with the ratio of the medians (general / rotated), whether the new entry's 90th percentile lies below the general's 10th, and whether
+the two results have the same bits at the end of each row.  (profiles/adjoint_rotated_time.txt)
+
+usage: python tools/adjoint_time.py [--planned | --channels | --rotated] [--launches N] [--out FILE]      (the table also goes to stdout)"""
 import argparse
 import os
 import subprocess
@@ -26,6 +31,8 @@ GEOMETRIES = [("cfg3", 8192, 8192, 8192.0, 2731.0, 17.5), ("wide8", 8192, 8192, 
               ("axis4", 4096, 4096, 4.0, 1.0, 0.0), ("quarter2.5", 4096, 4096, 2.5, 1.0, 90.0)]
 # the planned adjoint's rows: the two axis rows above, a flipped quadrant and a transposed up-sampling
 PLANNED_GEOMETRIES = [GEOMETRIES[3], GEOMETRIES[4], ("half180", 4096, 4096, 2.0, 1.0, 180.0), ("up2x270", 2048, 2048, 1.0, 2.0, 270.0)]
+# the planned adjoint at general rotations: the general-angle rows
+ROTATED_GEOMETRIES = GEOMETRIES[:3]
 # the interleaved adjoint's rows: (geometry name, mode)
 INTERLEAVED_ROWS = [("cfg3", 1), ("cfg3", 2), ("up2", 1)]
 
@@ -122,6 +129,55 @@ def child_planned(name, mode, launches):
         " ".join(tok for tok in aai.plan_shape(rq).split() if tok.split("=")[0] in ("flagged", "dense", "adjoint"))), flush=True)
 
 
+def child_rotated(name, mode, launches):
+    import numpy as np
+    import torch
+    import area_average_interpolation_amd as aai
+    aai.set_device(0)
+    _, W, H, sr, dr, ang = [g for g in ROTATED_GEOMETRIES if g[0] == name][0]
+    rq = aai.make_request(W, H, sr, dr, ((W - 1) / 2, (H - 1) / 2), ang, mode=mode)
+    lay = aai.query(rq)[2]
+    dW, dH = lay.dst_width, lay.dst_height
+    st = torch.cuda.current_stream().cuda_stream
+    y = torch.empty((dH, dW), dtype=torch.float32, device="cuda")
+    aai.synth_device(y.data_ptr(), dW, dH, dW, 2, st)
+    general = torch.empty((H, W), dtype=torch.float32, device="cuda")
+    rotated = torch.empty_like(general)
+    aai.adjoint_rotated_prepare(rq)
+    kernels = {}
+
+    def run_general():
+        aai.adjoint_device(rq, y.data_ptr(), dW, general.data_ptr(), W, st)
+        kernels["general"] = aai.last_kernel()
+
+    def run_rotated():
+        aai.adjoint_device(rq, y.data_ptr(), dW, rotated.data_ptr(), W, st, planned="any")
+        kernels["rotated"] = aai.last_kernel()
+
+    runs = {"general": run_general, "rotated": run_rotated}
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in runs}
+    for _ in range(launches):
+        for key, fn in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[key].append(a.elapsed_time(b))
+    same = torch.equal(general.view(torch.int32), rotated.view(torch.int32))
+    t = {k: np.array(v) for k, v in times.items()}
+    cell = lambda v: "%8.3f ms (%.3f..%.3f)" % (np.median(v), np.percentile(v, 10), np.percentile(v, 90))
+    clear = np.percentile(t["rotated"], 90) < np.percentile(t["general"], 10)
+    print("%-10s %-4s %5dx%-5d -> %5dx%-5d  general adjoint %s  rotated entry %s  general/rotated %5.2f  p90 < p10 %s  bits %s  [%s; %s]" % (
+        name, "area" if mode == aai.MODE_AREA else "fast", W, H, dW, dH, cell(t["general"]), cell(t["rotated"]),
+        np.median(t["general"]) / np.median(t["rotated"]), "yes" if clear else "NO", "same" if same else "DIFFERENT", kernels["rotated"],
+        " ".join(tok for tok in aai.plan_shape(rq).split() if tok.split("=")[0] in ("rot_adjoint", "knife"))), flush=True)
+
+
 def child(name, mode, launches):
     import numpy as np
     import torch
@@ -176,15 +232,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--planned", action="store_true")
     ap.add_argument("--channels", action="store_true")
+    ap.add_argument("--rotated", action="store_true")
     ap.add_argument("--child", nargs="+", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.launches < 20:
         ap.error("at least 20 timed launches")
-    if args.planned and args.channels:
-        ap.error("--planned and --channels are separate tables")
+    if args.planned + args.channels + args.rotated > 1:
+        ap.error("--planned, --channels and --rotated are separate tables")
     if args.child:
         if args.channels:
             child_channels(args.child[0], int(args.child[1]), int(args.child[2]), args.launches)
+        elif args.rotated:
+            child_rotated(args.child[0], int(args.child[1]), args.launches)
         else:
             (child_planned if args.planned else child)(args.child[0], int(args.child[1]), args.launches)
         return 0
@@ -206,13 +265,15 @@ def main():
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
         return 0
+    leg = ["--planned"] if args.planned else (["--rotated"] if args.rotated else [])
     lines = ["# median (10th..90th percentile) of %d launches each, device events, %s, one process per row"
-             % (args.launches, "forward, general adjoint and planned adjoint taking turns" if args.planned else "forward and adjoint alternating")]
+             % (args.launches, "forward, general adjoint and planned adjoint taking turns" if args.planned else
+                ("general adjoint and aai_adjoint_rotated_batch_device_f32 taking turns" if args.rotated else "forward and adjoint alternating"))]
     print(lines[0], flush=True)
-    for g in (PLANNED_GEOMETRIES if args.planned else GEOMETRIES):
+    for g in (PLANNED_GEOMETRIES if args.planned else (ROTATED_GEOMETRIES if args.rotated else GEOMETRIES)):
         for mode in (1, 2):
             # a fresh process per row, under its own time limit; a row that fails ends the run
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--launches", str(args.launches), "--child", g[0], str(mode)] + (["--planned"] if args.planned else []),
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--launches", str(args.launches), "--child", g[0], str(mode)] + leg,
                                capture_output=True, text=True, timeout=240)
             if r.returncode != 0:
                 sys.stderr.write(r.stdout + r.stderr)

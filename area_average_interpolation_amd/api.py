@@ -346,23 +346,43 @@ def adjoint_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter,
     return rc, "", gsrc
 
 
+_ADJOINT_INTERLEAVED_DEVICE_ENTRY = {"general": "aai_adjoint_interleaved_device_f32", "any": "aai_adjoint_rotated_interleaved_device_f32"}
+_ADJOINT_INTERLEAVED_HOST_ENTRY = {"general": "aai_adjoint_interleaved_f32", "any": "aai_adjoint_rotated_interleaved_f32"}
+
+
+def _planned_interleaved_kind(planned):
+    """planned=False | "any" of adjoint_interleaved_device / adjoint_interleaved_host -> which family of entries serves the call.  True is
+    refused: there is no interleaved transposed separable kernel to ask for."""
+    if planned is False:
+        return "general"
+    if isinstance(planned, str) and planned == "any":
+        return "any"
+    raise ValueError('planned must be False or "any" for the interleaved adjoint, got %r' % (planned,))
+
+
 def adjoint_interleaved_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None,
-                               dst_image_stride=0, src_image_stride=0):
+                               dst_image_stride=0, src_image_stride=0, planned=False):
     """aai_adjoint_interleaved_device_f32: gsrc = W(request)^T gdst per channel on device-resident fp32 images with `channels` (1..4)
     interleaved channels -- the transpose of what resample_interleaved_device computes (area and fast modes).  Element (x, y, c) of
     image b at b * image_stride + y * stride + x * channels + c; raw device pointers (ints), strides in elements, a hipStream_t
-    handle.  Channel c gets the bits adjoint_device gives plane c alone; a pair's weight is computed once for all channels."""
-    rc = L.load().aai_adjoint_interleaved_device_f32(_ref(request), 1 if batch is None else int(batch), int(channels), gdst_ptr, dst_stride,
-                                                     dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
+    handle.  Channel c gets the bits adjoint_device gives plane c alone; a pair's weight is computed once for all channels.
+    planned="any": aai_adjoint_rotated_interleaved_device_f32 -- the same bits; at a general rotation from the single-channel plan's cached
+    sums and the plain closed forms (the first call of a geometry builds them and synchronises, see adjoint_rotated_prepare, which
+    serves every channel count), at multiples of 90 degrees the general interleaved kernels.  planned=True raises ValueError: there is
+    no interleaved transposed separable kernel."""
+    fn = getattr(L.load(), _ADJOINT_INTERLEAVED_DEVICE_ENTRY[_planned_interleaved_kind(planned)])
+    rc = fn(_ref(request), 1 if batch is None else int(batch), int(channels), gdst_ptr, dst_stride,
+            dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
     if rc != L.OK:
         raise AaiError(rc, last_error())
 
 
 def adjoint_interleaved_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle,
-                             mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
-    """Host-buffer interleaved adjoint (aai_adjoint_interleaved_f32): gdst is the [dH, dW, C] gradient with respect to the output of
+                             mode=L.MODE_AREA, policy=L.POLICY_REFERENCE, planned=False):
+    """Host-buffer interleaved adjoint (aai_adjoint_interleaved_f32; planned="any": aai_adjoint_rotated_interleaved_f32): gdst is the [dH, dW, C] gradient with respect to the output of
     resample_interleaved_host(src of shape (H, W, C), ...), src_shape = (H, W) or (H, W, C); returns (code, message, gsrc [H, W, C]
     float32 or None)."""
+    entry = _ADJOINT_INTERLEAVED_HOST_ENTRY[_planned_interleaved_kind(planned)]
     lib = L.load()
     g = np.ascontiguousarray(gdst, dtype=np.float32)
     if g.ndim != 3:
@@ -378,7 +398,7 @@ def adjoint_interleaved_host(gdst, src_shape, src_resolution, dst_resolution, sr
     if g.shape[:2] != (lay.dst_height, lay.dst_width):
         raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width, C),))
     gsrc = np.empty((H, W, C), dtype=np.float32)
-    rc = lib.aai_adjoint_interleaved_f32(_ref(rq), C, g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
+    rc = getattr(lib, entry)(_ref(rq), C, g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
     if rc != L.OK:
         return rc, last_error(), None
     return rc, "", gsrc

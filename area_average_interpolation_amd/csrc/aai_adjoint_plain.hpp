@@ -81,4 +81,36 @@ AAI_HD double adjoint_plain_gather(const RotLaunch &r, int sx, int sy, const dou
     return acc;
 }
 
+// The same two passes for C interleaved channels (aai_adjoint_plain_multi.hip, tests/emulation/adjoint_plain_multi_emulation.cpp): S, K
+// and the plain weight of a pair do not depend on the channel, so a pair is enumerated, window-tested and integrated ONCE and each
+// channel then costs a load and a multiply-add -- channel c gets the operands adjoint_plain_gather gives plane c, in its order.
+// pass 1 per channel is adjoint_scaled<MODE>(S[d], gd[c]) itself: a division per channel.
+// pass 2: n has the channels innermost, [dH][dW][C], as in aai_adjoint_multi.hip
+template <int MODE, int C>
+AAI_HD void adjoint_plain_gather_multi(const RotLaunch &r, int sx, int sy, const double *n, double (&acc)[C])
+{
+    const double R = adjoint_reach(r), rL = 1.0 / r.side;
+    for (int c = 0; c < C; ++c) acc[c] = 0.0;
+    for (int jy = 0; jy < r.scale; ++jy)
+        for (int jx = 0; jx < r.scale; ++jx) {
+            int X, Y;
+            adjoint_virtual_pixel(r, sx, sy, jx, jy, X, Y);
+            int dxa, dxb, dya, dyb;
+            if (!adjoint_candidates(r, X, Y, R, rL, dxa, dxb, dya, dyb)) continue;
+            for (int dy = dya; dy <= dyb; ++dy)
+                for (int dx = dxa; dx <= dxb; ++dx) {
+                    double px, py;
+                    pixel_centre(r, dx, dy, px, py);
+                    int x0, x1, y0, y1;
+                    rot_window(r, px, py, x0, x1, y0, y1);
+                    if (X < x0 || X > x1 || Y < y0 || Y > y1) continue;          // the forward does not visit this pair
+                    const double w = adjoint_plain_pair_weight<MODE>(r, px, py, X, Y);
+                    if (w != 0.0) {
+                        const double *nd = n + ((int64_t)dy * r.dW + dx) * C;
+                        for (int c = 0; c < C; ++c) acc[c] += w * nd[c];
+                    }
+                }
+        }
+}
+
 }  // namespace aai

@@ -21,6 +21,7 @@
 #include "../../include/aai_adjoint_planned.h"
 #include "../../include/aai_adjoint_interleaved.h"
 #include "../../include/aai_adjoint_rotated.h"
+#include "../../include/aai_adjoint_rotated_interleaved.h"
 
 using namespace aai::engine;
 
@@ -283,8 +284,23 @@ int adjoint_host(AdjointEnqueue run, const aai_request *req, const float *gdst, 
     return finish(*req, g, layout);
 }
 
-// aai_adjoint_interleaved_f32: upload gdst, one launch on the null stream, download gsrc (dense rows of width x channels elements on the device)
-int adjoint_interleaved_host(const aai_request *req, int channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
+typedef int (*AdjointInterleavedEnqueue)(const aai_request &, const aai::Geometry &, int, int, const float *, int64_t, int64_t, float *, int64_t, int64_t, hipStream_t);
+
+// aai_adjoint_interleaved_device_f32 / aai_adjoint_rotated_interleaved_device_f32
+int adjoint_interleaved_device(AdjointInterleavedEnqueue run, const aai_request *req, int32_t batch, int32_t channels, const float *d_gdst, int64_t dst_stride,
+                               int64_t dst_image_stride, float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint_interleaved(req, batch, channels, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(run(*req, g, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+// aai_adjoint_interleaved_f32 / aai_adjoint_rotated_interleaved_f32: upload gdst, one launch on the null stream, download gsrc (dense rows of width x channels elements on the device)
+int adjoint_interleaved_host(AdjointInterleavedEnqueue run, const aai_request *req, int channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
 {
     aai::Geometry g;
     AAI_TRY(check_adjoint_interleaved(req, 1, channels, gdst, dst_stride, gsrc, src_stride, g));
@@ -295,7 +311,7 @@ int adjoint_interleaved_host(const aai_request *req, int channels, const float *
     AAI_HIP(dGdst.alloc(sizeof(float) * (size_t)rowDst * g.dH));
     AAI_HIP(dGsrc.alloc(sizeof(float) * (size_t)rowSrc * g.H));
     AAI_HIP(upload(dGdst, gdst, dst_stride, rowDst, g.dH, sizeof(float)));
-    AAI_TRY(enqueue_adjoint_interleaved(*req, g, 1, channels, dGdst.as<const float>(), rowDst, 0, dGsrc.as<float>(), rowSrc, 0, stream));
+    AAI_TRY(run(*req, g, 1, channels, dGdst.as<const float>(), rowDst, 0, dGsrc.as<float>(), rowSrc, 0, stream));
     AAI_HIP(hipStreamSynchronize(stream));
     AAI_HIP(download(gsrc, src_stride, dGsrc, rowSrc, g.H, sizeof(float)));
     return finish(*req, g, layout);
@@ -529,19 +545,28 @@ int aai_adjoint_interleaved_device_f32(const aai_request *req, int32_t batch, in
                                        const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
                                        float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
-    aai::Geometry g;
-    AAI_TRY(check_adjoint_interleaved(req, batch, channels, d_gdst, dst_stride, d_gsrc, src_stride, g));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue_adjoint_interleaved(*req, g, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    return adjoint_interleaved_device(enqueue_adjoint_interleaved, req, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride,
+                                      src_image_stride, stream);
 }
 
 int aai_adjoint_interleaved_f32(const aai_request *req, int32_t channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride,
                                 aai_layout *layout)
 {
-    return adjoint_interleaved_host(req, channels, gdst, dst_stride, gsrc, src_stride, layout);
+    return adjoint_interleaved_host(enqueue_adjoint_interleaved, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
+}
+
+int aai_adjoint_rotated_interleaved_device_f32(const aai_request *req, int32_t batch, int32_t channels,
+                                               const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                               float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    return adjoint_interleaved_device(enqueue_adjoint_rotated_interleaved, req, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride,
+                                      src_image_stride, stream);
+}
+
+int aai_adjoint_rotated_interleaved_f32(const aai_request *req, int32_t channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride,
+                                        aai_layout *layout)
+{
+    return adjoint_interleaved_host(enqueue_adjoint_rotated_interleaved, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
 int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)

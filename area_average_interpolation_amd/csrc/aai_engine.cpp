@@ -882,6 +882,56 @@ int enqueue_adjoint_rotated(const aai_request &rq, const Geometry &g, int batch,
     return AAI_OK;
 }
 
+int enqueue_adjoint_rotated_interleaved(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
+                                        int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+{
+    if (channels == 1) return enqueue_adjoint_rotated(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+    const int kernel = pick_kernel(rq, g);
+    if (kernel != AAI_KERNEL_ROTATED && kernel != AAI_KERNEL_FAST)      // reduced angle 0: there is no interleaved transposed separable kernel
+        return enqueue_adjoint_interleaved(rq, g, batch, channels, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+    PlanRef p;
+    {
+        // the plan enqueue_adjoint_rotated acquires -- the forward's SINGLE-channel plan under the forward's key: S and the source list
+        // do not depend on the channel count, so they are shared with single-channel calls
+        const int rc = acquire_plan(rq, g, -1, -1, 1, rot_form(rq, g, 1, aai::SRC_F32, g.W), &p, /*onCallerStream*/ true, stream);
+        if (rc != AAI_OK) return rc;
+        std::lock_guard<std::mutex> lock(p->build);
+        const int rt = build_rot_adjoint_tables(*p);
+        if (rt != AAI_OK) return rt;
+    }
+    if (p->rotAdjState != 1)
+        return enqueue_adjoint_interleaved(rq, g, batch, channels, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+
+    std::lock_guard<std::mutex> lock(p->launch);
+    const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
+    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
+    // scratch: one fp64 image of the dst size times the channels per image in flight, chunked as in enqueue_adjoint_channels
+    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * (size_t)channels * sizeof(double);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch, kMaxGridZ), ((size_t)1 << 30) / imageBytes));
+    hipMemPool_t scratch = nullptr;
+    {
+        const int rc = adjoint_scratch_pool(p->device, &scratch);
+        if (rc != AAI_OK) return rc;
+    }
+    double *n = nullptr;
+    AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
+    const char *name = "";
+    const bool listed = p->adjSrcCount != 0;
+    hipError_t e = hipSuccess;
+    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
+        const int nb = std::min(batch - b0, chunk);
+        const float *gd = dGdst + (int64_t)b0 * dstImageStride;
+        float *gs = dGsrc + (int64_t)b0 * srcImageStride;
+        e = aai::launch_adjoint_plain_multi(r, channels, nb, gd, dv, p->dAdjSums, n, gs, sv, static_cast<const uint2 *>(p->dAdjSrcList), p->adjSrcCount,
+                                            stream, &name);
+    }
+    const hipError_t ef = hipFreeAsync(n, stream);
+    g_lastKernel = listed ? std::string(name) + "+listed" : std::string(name);
+    if (e != hipSuccess) return hip_fail(e, name);
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    return AAI_OK;
+}
+
 int require_device()
 {
     int n = 0;

@@ -176,5 +176,17 @@ int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const f
 int enqueue_adjoint_interleaved(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
                                 int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 
+// The planned adjoint at general rotations for `channels` = 1..4 interleaved channels (aai_adjoint_rotated_interleaved_*; the caller has
+// checked the arguments).  One channel: enqueue_adjoint_rotated, identical bits.  Reduced angle 0: enqueue_adjoint_interleaved, the
+// GENERAL interleaved adjoint with its bits -- an interleaved transposed separable kernel is out of scope (the single-channel entry
+// differs there: it forwards to the fp32 axis kernel).  Otherwise the plan enqueue_adjoint_rotated acquires (the forward's
+// single-channel plan, same key, its tables built on first need: blocks; S and the source list are shared with single-channel calls,
+// no second copy and no new per-plan memory), then per chunk the element-wise pass 1, the plain gather with `channels` accumulators
+// and, where the plan lists source pixels, the general multi-channel gather over them (aai_adjoint_plain_multi.hip).  A plan in
+// rotAdjState 2: enqueue_adjoint_interleaved.  Scratch of dW x dH x channels doubles per image in flight, the chunk sized from that as
+// in enqueue_adjoint_interleaved.  Only enqueues once the tables exist.
+int enqueue_adjoint_rotated_interleaved(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
+                                        int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
+
 }  // namespace engine
 }  // namespace aai

@@ -140,6 +140,12 @@ hipError_t launch_adjoint_knife_list(const RotLaunch &r, const unsigned char *kn
 // `batch` <= 65535; n holds batch x dH x dW doubles.  Only enqueues.
 hipError_t launch_adjoint_plain(const RotLaunch &r, int batch, const float *gdst, ImageView dv, const double *S, double *n, float *gsrc, ImageView sv,
                                 hipStream_t stream, const char **kernelName);
+// the same for `channels` = 2..4 interleaved channels (aai_adjoint_plain_multi.hip): the element-wise pass 1 over rows of dW x channels
+// elements, the plain gather with `channels` accumulators, and -- where nSrc != 0 -- the general multi-channel gather over the plan's
+// listed source pixels, which overwrites them.  Channel c gets the bits launch_adjoint_plain (+ launch_adjoint_gather_listed) gives
+// plane c.  n holds batch x dH x dW x channels doubles, channels innermost.  `batch` <= 65535.  Only enqueues.
+hipError_t launch_adjoint_plain_multi(const RotLaunch &r, int channels, int batch, const float *gdst, ImageView dv, const double *S, double *n, float *gsrc,
+                                      ImageView sv, const uint2 *srcList, unsigned nSrc, hipStream_t stream, const char **kernelName);
 
 // ---- the transpose of K1 (aai_axis_adjoint.hip): the adjoint at rotations by multiples of 90 degrees, fp32, from the forward's tables
 struct AxisAdjointLaunch {

@@ -3,7 +3,8 @@
 ``resample(x, ...)`` runs the library's forward (aai_resample_batch_device_f32) on a device-resident fp32 tensor and is a
 ``torch.autograd.Function``: its backward is the library's adjoint (aai_adjoint_batch_device_f32), gsrc = W^T gdst with the
 forward's own weights -- not an approximation through ``grid_sample`` (``planned_backward=True``: the planned adjoint,
-aai_adjoint_planned_batch_device_f32; ``"any"``: aai_adjoint_rotated_batch_device_f32, planned at every rotation).  Both launch on ``torch.cuda.current_stream()`` of the
+aai_adjoint_planned_batch_device_f32; ``"any"``: aai_adjoint_rotated_batch_device_f32, planned at every rotation; ``"interleaved"``:
+``"any"`` plus aai_adjoint_rotated_interleaved_device_f32 for channels_last tensors at general rotations).  Both launch on ``torch.cuda.current_stream()`` of the
 tensor's device and only enqueue work.
 
 torch is imported here, not by the package: ``import area_average_interpolation_amd`` works without it.
@@ -50,12 +51,25 @@ def _ensure_rotated_adjoint_prepared(rq):
     api.adjoint_rotated_prepare(rq)
 
 
+def _ensure_interleaved_adjoint_prepared(rq):
+    """planned_backward="interleaved" on the interleaved route: the tables of aai_adjoint_rotated_interleaved_device_f32 live on the
+    SINGLE-channel plan of the geometry, which the interleaved forward (prepared for C channels) does not build.  Build both
+    (aai_adjoint_rotated_prepare) in the forward, outside any stream capture."""
+    tokens = api.plan_shape(rq).split()
+    if tokens and "rot_adjoint=none" not in tokens:
+        return
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('resample(planned_backward="interleaved"): this geometry has no adjoint tables on this device yet and the current '
+                           "stream is being captured; call resample() (or adjoint_rotated_prepare()) once with the same geometry before capturing")
+    api.adjoint_rotated_prepare(rq)
+
+
 def _normalise_planned(planned_backward):
-    """False | True | "any" (anything else that is a string raises)"""
+    """False | True | "any" | "interleaved" (anything else that is a string raises)"""
     if isinstance(planned_backward, str):
-        if planned_backward != "any":
-            raise ValueError('planned_backward must be False, True or "any", got %r' % (planned_backward,))
-        return "any"
+        if planned_backward not in ("any", "interleaved"):
+            raise ValueError('planned_backward must be False, True, "any" or "interleaved", got %r' % (planned_backward,))
+        return planned_backward
     return bool(planned_backward)
 
 
@@ -97,13 +111,16 @@ class _ResampleInterleaved(torch.autograd.Function):
     """(B, C, H, W) dense in torch.channels_last, 2 <= C <= 4: the NHWC storage is the library's interleaved layout, nothing is copied"""
 
     @staticmethod
-    def forward(ctx, x, rq, lay):
+    def forward(ctx, x, rq, lay, planned=False):
+        """planned: False (the general interleaved adjoint) or "any" (aai_adjoint_rotated_interleaved_device_f32)"""
         B, C, H, W = x.shape
         dH, dW = lay.dst_height, lay.dst_width
         y = torch.empty((B, C, dH, dW), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        ctx.rq, ctx.src_shape = rq, (B, C, H, W)
+        ctx.rq, ctx.src_shape, ctx.planned = rq, (B, C, H, W), planned
         with torch.cuda.device(x.device):
             _ensure_prepared(rq, C)
+            if planned and ctx.needs_input_grad[0]:
+                _ensure_interleaved_adjoint_prepared(rq)
             api.resample_interleaved_device(rq, C, x.data_ptr(), W * C, y.data_ptr(), dW * C, stream=torch.cuda.current_stream().cuda_stream,
                                             batch=B, src_image_stride=H * W * C, dst_image_stride=dH * dW * C)
         return y
@@ -119,8 +136,8 @@ class _ResampleInterleaved(torch.autograd.Function):
         dH, dW = gy.shape[2], gy.shape[3]
         with torch.cuda.device(gy.device):
             api.adjoint_interleaved_device(ctx.rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, stream=torch.cuda.current_stream().cuda_stream,
-                                           batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C)
-        return gx, None, None
+                                           batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C, planned=ctx.planned)
+        return gx, None, None, None
 
 
 def _query(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy):
@@ -140,6 +157,10 @@ def _resample_nchw(x, geometry, mode, policy, planned):
     if x.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
         raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
     interleaved = 2 <= C <= 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
+    if planned == "interleaved":
+        if interleaved and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST):
+            return _ResampleInterleaved.apply(x, rq, lay, "any"), iso       # zero-copy AND the planned backward
+        planned = "any"              # every other input: exactly "any"
     if interleaved and planned and lay.kernel == L.KERNEL_AXIS:
         interleaved = False          # the planned adjoint is single-channel, and far faster there than the interleaved gather
     if interleaved and planned == "any" and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST):
@@ -166,9 +187,19 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     inside a stream capture a geometry without them raises RuntimeError, like a geometry without a plan.  "any" -- the backward is
     aai_adjoint_rotated_batch_device_f32: exactly True at multiples of 90 degrees; at every other rotation the default's BITS from the
     plan's cached sums (8 bytes per dst pixel on the device) and the plain closed forms, and with an x that requires grad the forward
-    builds those tables (aai_adjoint_rotated_prepare; the same rule inside a stream capture).
+    builds those tables (aai_adjoint_rotated_prepare; the same rule inside a stream capture).  "interleaved" -- exactly "any" for
+    every input but one: a (B, C, H, W) tensor dense in torch.channels_last with 2 <= C <= 4 at a geometry the rotated area / fast
+    kernels serve keeps the zero-copy interleaved route AND gets a planned backward, aai_adjoint_rotated_interleaved_device_f32 (the
+    same tables, on the single-channel plan, built by the forward when x requires grad; the same rule inside a stream capture).  Any
+    other string raises ValueError.
 
-    (B, C, H, W) input takes one of two routes, every plane resampled with the same geometry:
+    (B, C, H, W) input takes one of two routes, every plane resampled with the same geometry.  Which one, by planned_backward
+    (cl = dense in channels_last with 2 <= C <= 4; "other" = bilinear / bicubic):
+      geometry served by      False              True               "any"              "interleaved"
+      separable kernel, cl    interleaved        planar             planar             planar
+      rotated / fast, cl      interleaved        interleaved        planar             interleaved, planned backward
+      other, cl               interleaved        interleaved        interleaved        interleaved
+      any, not cl             planar             planar             planar             planar
       planar       x.contiguous() viewed as (B * C, H, W) through the 3-D operator and reshaped back: the 3-D operator's bits plane by
                    plane, planned_backward honoured.  Every input the interleaved route does not take, channels_last tensors with
                    C = 1 or C > 4 among them.
@@ -181,6 +212,15 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
                    the planar route is taken -- the planned adjoint is single-channel and one to two orders of magnitude faster
                    there than the general gather, which the interleaved adjoint is.  The same holds for planned_backward="any" at
                    every geometry its single-channel path serves (the separable kernel's, and the rotated area / fast kernels').
+                   planned_backward="interleaved" lifts the second half of the exception: at a geometry the rotated area / fast
+                   kernels serve the route stays interleaved and the backward is aai_adjoint_rotated_interleaved_device_f32 on a
+                   channels_last gy -- y and x.grad are channels_last and have the bits of this route's default (y: the interleaved
+                   forward's; x.grad: per channel the default single-channel adjoint's, which are also the "any" planar route's).
+                   At the separable kernel's geometries it stays planar: the transposed separable kernel is single-channel.
+                   Measured on an MI355X for C = 3 and 4 (profiles/adjoint_rotated_interleaved_time.txt, one run; DESIGN.md section 9
+                   quotes it): the new backward is 1.9-4.2x faster than the general interleaved backward and 2.5-3.5x faster than C
+                   planned single-channel backwards on planes split beforehand (the planar route's permutes not counted), with
+                   identical bits in every row.
     B == 0 or C == 0 returns an empty tensor of the output's shape without a launch."""
     if not isinstance(x, torch.Tensor):
         raise TypeError("resample() takes a torch.Tensor")
@@ -199,5 +239,8 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         raise api.AaiError(rc, msg)
     if xb.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
         raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
-    y = _Resample.apply(xb, rq, lay, _normalise_planned(planned_backward))
+    planned = _normalise_planned(planned_backward)
+    if planned == "interleaved":
+        planned = "any"              # there are no channels to interleave
+    y = _Resample.apply(xb, rq, lay, planned)
     return (y if x.dim() == 3 else y.squeeze(0)), (lay.dst_iso_x, lay.dst_iso_y)

@@ -44,7 +44,9 @@ extern "C" {
  * rotation aai_adjoint_planned_* and aai_adjoint_prepare still build no plan.
  * MEASURED on an MI355X against aai_adjoint_batch_device_f32 taking turns in the same process (profiles/adjoint_rotated_time.txt, one run;
  * DESIGN.md section 9 quotes it), general / new, median of 24 launches: 8192 x 8192 -> 3426 x 3426 at 17.5 degrees 3.7 (area: 7.54 -> 2.04
- * ms) and 2.2 (fast); 8:1 at 17.5 degrees 3.3 and 2.1; x2 up-sampling at 30 degrees 5.0 and 2.5; identical bits in every row. */
+ * ms) and 2.2 (fast); 8:1 at 17.5 degrees 3.3 and 2.1; x2 up-sampling at 30 degrees 5.0 and 2.5; identical bits in every row.
+ * aai_adjoint_rotated_prepare also prepares the interleaved entries of aai_adjoint_rotated_interleaved.h: they use this plan and these
+ * tables for every channel count and have no prepare entry of their own. */
 int aai_adjoint_rotated_prepare(const aai_request *req);
 int aai_adjoint_rotated_batch_device_f32(const aai_request *req, int32_t batch,
                                          const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,

@@ -17,7 +17,13 @@ unchanged general entry on ROTATED_GEOMETRIES -- the general-angle rows of the f
 with the ratio of the medians (general / rotated), whether the new entry's 90th percentile lies below the general's 10th, and whether
 the two results have the same bits at the end of each row.  (profiles/adjoint_rotated_time.txt)
 
-usage: python tools/adjoint_time.py [--planned | --channels | --rotated] [--launches N] [--out FILE]      (the table also goes to stdout)"""
+--rotated --channels: the interleaved planned adjoint at general rotations (aai_adjoint_rotated_interleaved_device_f32, after
+aai_adjoint_rotated_prepare) on ROTATED_INTERLEAVED_ROWS with C = 3 and C = 4, three legs taking turns -- (a) the new entry, (b)
+aai_adjoint_interleaved_device_f32, the general interleaved adjoint, (c) C calls of aai_adjoint_rotated_batch_device_f32 on planes split
+beforehand (the split is not timed) -- with the ratios of the medians (b)/(a) and (c)/(a), whether (a)'s 90th percentile lies below
+(b)'s 10th, and whether (a) and (b) have the same bits at the end of each row.  (profiles/adjoint_rotated_interleaved_time.txt)
+
+usage: python tools/adjoint_time.py [--planned | --channels | --rotated | --rotated --channels] [--launches N] [--out FILE]      (the table also goes to stdout)"""
 import argparse
 import os
 import subprocess
@@ -35,6 +41,68 @@ PLANNED_GEOMETRIES = [GEOMETRIES[3], GEOMETRIES[4], ("half180", 4096, 4096, 2.0,
 ROTATED_GEOMETRIES = GEOMETRIES[:3]
 # the interleaved adjoint's rows: (geometry name, mode)
 INTERLEAVED_ROWS = [("cfg3", 1), ("cfg3", 2), ("up2", 1)]
+# the interleaved planned adjoint's rows: (geometry name, mode)
+ROTATED_INTERLEAVED_ROWS = [("cfg3", 1), ("cfg3", 2), ("wide8", 1), ("up2", 1)]
+
+
+def child_rotated_channels(name, mode, channels, launches):
+    import numpy as np
+    import torch
+    import area_average_interpolation_amd as aai
+    aai.set_device(0)
+    _, W, H, sr, dr, ang = [g for g in GEOMETRIES if g[0] == name][0]
+    C = channels
+    rq = aai.make_request(W, H, sr, dr, ((W - 1) / 2, (H - 1) / 2), ang, mode=mode)
+    lay = aai.query(rq)[2]
+    dW, dH = lay.dst_width, lay.dst_height
+    st = torch.cuda.current_stream().cuda_stream
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    gd = torch.rand((dH, dW, C), dtype=torch.float32, device="cuda", generator=gen)
+    planes = gd.permute(2, 0, 1).contiguous()                       # split beforehand: not part of any leg
+    new = torch.empty((H, W, C), dtype=torch.float32, device="cuda")
+    general = torch.empty_like(new)
+    ps = torch.empty((C, H, W), dtype=torch.float32, device="cuda")
+    aai.adjoint_rotated_prepare(rq)                                 # serves every channel count
+    kernels = {}
+
+    def run_new():
+        aai.adjoint_interleaved_device(rq, C, gd.data_ptr(), dW * C, new.data_ptr(), W * C, st, planned="any")
+        kernels["new"] = aai.last_kernel()
+
+    def run_general():
+        aai.adjoint_interleaved_device(rq, C, gd.data_ptr(), dW * C, general.data_ptr(), W * C, st)
+        kernels["general"] = aai.last_kernel()
+
+    def run_planar():
+        for c in range(C):
+            aai.adjoint_device(rq, planes[c].data_ptr(), dW, ps[c].data_ptr(), W, st, planned="any")
+        kernels["planar"] = aai.last_kernel()
+
+    runs = {"new": run_new, "general": run_general, "planar": run_planar}
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in runs}
+    for _ in range(launches):
+        for key, fn in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[key].append(a.elapsed_time(b))
+    same = torch.equal(new.view(torch.int32), general.view(torch.int32))
+    same_planar = torch.equal(new.permute(2, 0, 1).contiguous().view(torch.int32), ps.view(torch.int32))
+    t = {k: np.array(v) for k, v in times.items()}
+    cell = lambda v: "%8.3f ms (%.3f..%.3f)" % (np.median(v), np.percentile(v, 10), np.percentile(v, 90))
+    clear = np.percentile(t["new"], 90) < np.percentile(t["general"], 10)
+    print("%-10s %-4s C=%d %5dx%-5d -> %5dx%-5d  (a) new entry %s  (b) general interleaved %s  (c) %d planned single-channel calls %s  "
+          "(b)/(a) %5.2f  (c)/(a) %5.2f  p90(a) < p10(b) %s  bits (a)=(b) %s (a)=(c) %s  [%s; %s; %s]" % (
+              name, "area" if mode == aai.MODE_AREA else "fast", C, W, H, dW, dH, cell(t["new"]), cell(t["general"]), C, cell(t["planar"]),
+              np.median(t["general"]) / np.median(t["new"]), np.median(t["planar"]) / np.median(t["new"]), "yes" if clear else "NO",
+              "same" if same else "DIFFERENT", "same" if same_planar else "DIFFERENT", kernels["new"], kernels["planar"],
+              " ".join(tok for tok in aai.plan_shape(rq).split() if tok.split("=")[0] in ("rot_adjoint", "knife"))), flush=True)
 
 
 def child_channels(name, mode, channels, launches):
@@ -237,10 +305,13 @@ def main():
     args = ap.parse_args()
     if args.launches < 20:
         ap.error("at least 20 timed launches")
-    if args.planned + args.channels + args.rotated > 1:
-        ap.error("--planned, --channels and --rotated are separate tables")
+    both = args.rotated and args.channels                      # the interleaved planned adjoint's table
+    if args.planned + args.channels + args.rotated > 1 and not (both and not args.planned):
+        ap.error("--planned, --channels and --rotated are separate tables (--rotated --channels is a fourth)")
     if args.child:
-        if args.channels:
+        if both:
+            child_rotated_channels(args.child[0], int(args.child[1]), int(args.child[2]), args.launches)
+        elif args.channels:
             child_channels(args.child[0], int(args.child[1]), int(args.child[2]), args.launches)
         elif args.rotated:
             child_rotated(args.child[0], int(args.child[1]), args.launches)
@@ -248,13 +319,16 @@ def main():
             (child_planned if args.planned else child)(args.child[0], int(args.child[1]), args.launches)
         return 0
     if args.channels:
-        lines = ["# median (10th..90th percentile) of %d launches each, device events, the interleaved call and the C single-channel calls "
-                 "on pre-split planes taking turns, one process per row" % args.launches]
+        lines = ["# median (10th..90th percentile) of %d launches each, device events, %s taking turns, one process per row" % (
+            args.launches, "(a) aai_adjoint_rotated_interleaved_device_f32, (b) aai_adjoint_interleaved_device_f32 and (c) C calls of "
+            "aai_adjoint_rotated_batch_device_f32 on pre-split planes" if both else
+            "the interleaved call and the C single-channel calls on pre-split planes")]
         print(lines[0], flush=True)
-        for name, mode in INTERLEAVED_ROWS:
+        for name, mode in (ROTATED_INTERLEAVED_ROWS if both else INTERLEAVED_ROWS):
             for channels in (3, 4):
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--channels", "--launches", str(args.launches),
-                                    "--child", name, str(mode), str(channels)], capture_output=True, text=True, timeout=240)
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--channels"] + (["--rotated"] if both else []) +
+                                   ["--launches", str(args.launches), "--child", name, str(mode), str(channels)],
+                                   capture_output=True, text=True, timeout=240)
                 if r.returncode != 0:
                     sys.stderr.write(r.stdout + r.stderr)
                     return r.returncode or 1

@@ -277,17 +277,65 @@ def resample_device(request, src_ptr, src_stride, dst_ptr, dst_stride, stream=0,
         raise AaiError(rc, last_error())
 
 
-_ADJOINT_DEVICE_ENTRY = {"general": "aai_adjoint_batch_device_f32", "planned": "aai_adjoint_planned_batch_device_f32", "any": "aai_adjoint_rotated_batch_device_f32"}
-_ADJOINT_HOST_ENTRY = {"general": "aai_adjoint_f32", "planned": "aai_adjoint_planned_f32", "any": "aai_adjoint_rotated_f32"}
+# (interleaved entry?, planned kind) -> (device entry, host entry).  There is no ("planned") row for the interleaved entries: no
+# interleaved transposed separable kernel exists to ask for.
+_ADJOINT_ENTRY = {
+    (False, "general"): ("aai_adjoint_batch_device_f32", "aai_adjoint_f32"),
+    (False, "planned"): ("aai_adjoint_planned_batch_device_f32", "aai_adjoint_planned_f32"),
+    (False, "any"): ("aai_adjoint_rotated_batch_device_f32", "aai_adjoint_rotated_f32"),
+    (True, "general"): ("aai_adjoint_interleaved_device_f32", "aai_adjoint_interleaved_f32"),
+    (True, "any"): ("aai_adjoint_rotated_interleaved_device_f32", "aai_adjoint_rotated_interleaved_f32"),
+}
 
 
-def _planned_kind(planned):
-    """planned=False | True | "any" of adjoint_device / adjoint_host -> which family of entries serves the call"""
+def _planned_kind(planned, interleaved=False):
+    """planned=False | True | "any" of the adjoint wrappers -> which family of entries serves the call.  The interleaved wrappers take
+    False or "any" only; True is refused there."""
+    if interleaved:
+        if planned is False:
+            return "general"
+        if isinstance(planned, str) and planned == "any":
+            return "any"
+        raise ValueError('planned must be False or "any" for the interleaved adjoint, got %r' % (planned,))
     if isinstance(planned, str):
         if planned != "any":
             raise ValueError('planned must be False, True or "any", got %r' % (planned,))
         return "any"
     return "planned" if planned else "general"
+
+
+def _planned_interleaved_kind(planned):
+    return _planned_kind(planned, interleaved=True)
+
+
+def _adjoint_device(interleaved, planned, request, batch, channels, gdst_ptr, dst_stride, dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream):
+    """the device entry of _ADJOINT_ENTRY; the interleaved entries take the channel count after the batch"""
+    fn = getattr(L.load(), _ADJOINT_ENTRY[interleaved, _planned_kind(planned, interleaved)][0])
+    rc = fn(_ref(request), 1 if batch is None else int(batch), *((int(channels),) if interleaved else ()), gdst_ptr, dst_stride,
+            dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def _adjoint_host(interleaved, planned, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy):
+    """the host entry of _ADJOINT_ENTRY on gdst = [dH, dW] (single-channel) or [dH, dW, C] (interleaved)"""
+    lib = L.load()
+    H, W = int(src_shape[0]), int(src_shape[1])
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None
+    g = np.ascontiguousarray(gdst, dtype=np.float32)
+    tail = g.shape[2:] if interleaved else ()                      # () or (C,)
+    C = tail[0] if interleaved else 1
+    if (g.shape[:2] if interleaved else g.shape) != (lay.dst_height, lay.dst_width):
+        raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width) + tail,))
+    gsrc = np.empty((H, W) + tail, dtype=np.float32)
+    fn = getattr(lib, _ADJOINT_ENTRY[interleaved, _planned_kind(planned, interleaved)][1])
+    rc = fn(_ref(rq), *((C,) if interleaved else ()), g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
+    if rc != L.OK:
+        return rc, last_error(), None
+    return rc, "", gsrc
 
 
 def adjoint_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None,
@@ -301,11 +349,7 @@ def adjoint_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0
     planned="any": aai_adjoint_rotated_batch_device_f32 -- one entry for every rotation: what planned=True does at multiples of 90
     degrees, and at every other rotation the general adjoint's bits from the plan's cached sums and the plain closed forms (the
     first call of a geometry builds them and synchronises, see adjoint_rotated_prepare)."""
-    fn = getattr(L.load(), _ADJOINT_DEVICE_ENTRY[_planned_kind(planned)])
-    rc = fn(_ref(request), 1 if batch is None else int(batch), gdst_ptr, dst_stride, dst_image_stride,
-            gsrc_ptr, src_stride, src_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _adjoint_device(False, planned, request, batch, 1, gdst_ptr, dst_stride, dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
 
 
 def adjoint_prepare(request):
@@ -329,35 +373,7 @@ def adjoint_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter,
                  mode=L.MODE_AREA, policy=L.POLICY_REFERENCE, planned=False):
     """Host-buffer adjoint (aai_adjoint_f32; planned=True: aai_adjoint_planned_f32; planned="any": aai_adjoint_rotated_f32): gdst is the [dH, dW] gradient with respect to
     the output of resample_host(src of shape src_shape = (H, W), ...); returns (code, message, gsrc [H, W] float32 or None)."""
-    lib = L.load()
-    H, W = int(src_shape[0]), int(src_shape[1])
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None
-    g = np.ascontiguousarray(gdst, dtype=np.float32)
-    if g.shape != (lay.dst_height, lay.dst_width):
-        raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width),))
-    gsrc = np.empty((H, W), dtype=np.float32)
-    fn = getattr(lib, _ADJOINT_HOST_ENTRY[_planned_kind(planned)])
-    rc = fn(_ref(rq), g.ctypes.data, max(lay.dst_width, 1), gsrc.ctypes.data, W, None)
-    if rc != L.OK:
-        return rc, last_error(), None
-    return rc, "", gsrc
-
-
-_ADJOINT_INTERLEAVED_DEVICE_ENTRY = {"general": "aai_adjoint_interleaved_device_f32", "any": "aai_adjoint_rotated_interleaved_device_f32"}
-_ADJOINT_INTERLEAVED_HOST_ENTRY = {"general": "aai_adjoint_interleaved_f32", "any": "aai_adjoint_rotated_interleaved_f32"}
-
-
-def _planned_interleaved_kind(planned):
-    """planned=False | "any" of adjoint_interleaved_device / adjoint_interleaved_host -> which family of entries serves the call.  True is
-    refused: there is no interleaved transposed separable kernel to ask for."""
-    if planned is False:
-        return "general"
-    if isinstance(planned, str) and planned == "any":
-        return "any"
-    raise ValueError('planned must be False or "any" for the interleaved adjoint, got %r' % (planned,))
+    return _adjoint_host(False, planned, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
 
 
 def adjoint_interleaved_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None,
@@ -370,11 +386,7 @@ def adjoint_interleaved_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr
     sums and the plain closed forms (the first call of a geometry builds them and synchronises, see adjoint_rotated_prepare, which
     serves every channel count), at multiples of 90 degrees the general interleaved kernels.  planned=True raises ValueError: there is
     no interleaved transposed separable kernel."""
-    fn = getattr(L.load(), _ADJOINT_INTERLEAVED_DEVICE_ENTRY[_planned_interleaved_kind(planned)])
-    rc = fn(_ref(request), 1 if batch is None else int(batch), int(channels), gdst_ptr, dst_stride,
-            dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _adjoint_device(True, planned, request, batch, channels, gdst_ptr, dst_stride, dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
 
 
 def adjoint_interleaved_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle,
@@ -382,26 +394,13 @@ def adjoint_interleaved_host(gdst, src_shape, src_resolution, dst_resolution, sr
     """Host-buffer interleaved adjoint (aai_adjoint_interleaved_f32; planned="any": aai_adjoint_rotated_interleaved_f32): gdst is the [dH, dW, C] gradient with respect to the output of
     resample_interleaved_host(src of shape (H, W, C), ...), src_shape = (H, W) or (H, W, C); returns (code, message, gsrc [H, W, C]
     float32 or None)."""
-    entry = _ADJOINT_INTERLEAVED_HOST_ENTRY[_planned_interleaved_kind(planned)]
-    lib = L.load()
+    _planned_kind(planned, interleaved=True)                 # (a bad `planned` is reported before a bad gdst)
     g = np.ascontiguousarray(gdst, dtype=np.float32)
     if g.ndim != 3:
         raise ValueError("gdst must be a [dH, dW, C] array")
-    C = g.shape[2]
-    if len(src_shape) == 3 and int(src_shape[2]) != C:
-        raise ValueError("gdst has %d channels, src_shape %d" % (C, int(src_shape[2])))
-    H, W = int(src_shape[0]), int(src_shape[1])
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None
-    if g.shape[:2] != (lay.dst_height, lay.dst_width):
-        raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width, C),))
-    gsrc = np.empty((H, W, C), dtype=np.float32)
-    rc = getattr(lib, entry)(_ref(rq), C, g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
-    if rc != L.OK:
-        return rc, last_error(), None
-    return rc, "", gsrc
+    if len(src_shape) == 3 and int(src_shape[2]) != g.shape[2]:
+        raise ValueError("gdst has %d channels, src_shape %d" % (g.shape[2], int(src_shape[2])))
+    return _adjoint_host(True, planned, g, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
 
 
 def resample_multi_device(request, shards, src_stride, src_image_stride, dst_stride, dst_image_stride):

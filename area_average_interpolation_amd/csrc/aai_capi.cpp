@@ -94,38 +94,42 @@ int check_adjoint_request(const aai_request *rq, int batch, aai::Geometry &g)
     if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the adjoint.");
     return AAI_OK;
 }
-// ... and the images'
-int check_adjoint(const aai_request *rq, int batch, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride, aai::Geometry &g)
+// ... and the images'.  The interleaved entries (aai_adjoint_interleaved_*, aai_adjoint_rotated_interleaved_*) check the channel count
+// right after the request, as the forward's interleaved entries report it, and the row length before the pointers; the single-channel
+// entries check neither.  Strides in elements of `channels` per pixel.
+int check_adjoint(const aai_request *rq, int batch, bool interleaved, int channels, const void *gdst, int64_t dstStride, const void *gsrc,
+                  int64_t srcStride, aai::Geometry &g)
 {
+    if (interleaved) {
+        AAI_TRY(check_request(rq));
+        AAI_TRY(check_channels(channels));
+    }
     AAI_TRY(check_adjoint_request(rq, batch, g));
-    AAI_TRY(check_pointers(gdst, gsrc));
-    return check_strides(g, 1, srcStride, dstStride);
-}
-
-// the interleaved adjoint: the channel count right after the request (as the forward's interleaved entries report it), then what every
-// adjoint entry checks, then the row length and the strides in elements of `channels` per pixel
-int check_adjoint_interleaved(const aai_request *rq, int batch, int channels, const void *gdst, int64_t dstStride, const void *gsrc, int64_t srcStride,
-                              aai::Geometry &g)
-{
-    AAI_TRY(check_request(rq));
-    AAI_TRY(check_channels(channels));
-    AAI_TRY(check_adjoint_request(rq, batch, g));
-    AAI_TRY(check_row_length(g, channels));
+    if (interleaved) AAI_TRY(check_row_length(g, channels));
     AAI_TRY(check_pointers(gdst, gsrc));
     return check_strides(g, channels, srcStride, dstStride);
 }
 
-typedef int (*AdjointEnqueue)(const aai_request &, const aai::Geometry &, int, const float *, int64_t, int64_t, float *, int64_t, int64_t, hipStream_t);
-
-// aai_adjoint_batch_device_f32 / aai_adjoint_planned_batch_device_f32 / aai_adjoint_rotated_batch_device_f32
-int adjoint_device(AdjointEnqueue run, const aai_request *req, int32_t batch, const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
-                   float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+// every device entry of the adjoint; the single-channel entries pass interleaved = false, channels = 1
+int adjoint_device(AdjointFamily family, bool interleaved, const aai_request *req, int32_t batch, int32_t channels, const float *d_gdst,
+                   int64_t dst_stride, int64_t dst_image_stride, float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(req, batch, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    AAI_TRY(check_adjoint(req, batch, interleaved, channels, d_gdst, dst_stride, d_gsrc, src_stride, g));
     if (batch == 0) { g_lastError.clear(); return AAI_OK; }
     AAI_TRY(require_device());
-    AAI_TRY(run(*req, g, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
+    AAI_TRY(enqueue_adjoint(family, *req, g, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+// aai_adjoint_prepare / aai_adjoint_rotated_prepare
+int adjoint_prepare(AdjointFamily family, const aai_request *req)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint_request(req, 1, g));
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue_adjoint(family, *req, g, 0, 1, nullptr, 0, 0, nullptr, 0, 0, nullptr));
     g_lastError.clear();
     return AAI_OK;
 }
@@ -267,43 +271,13 @@ bool is_page_locked(const void *p)
     return attr.type == hipMemoryTypeHost;
 }
 
-// aai_adjoint_f32 / aai_adjoint_planned_f32 / aai_adjoint_rotated_f32: upload gdst, one launch on the null stream, download gsrc
-int adjoint_host(AdjointEnqueue run, const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
+// every host entry of the adjoint: upload gdst, one launch on the null stream, download gsrc (dense rows of width x channels elements on
+// the device); the single-channel entries pass interleaved = false, channels = 1
+int adjoint_host(AdjointFamily family, bool interleaved, const aai_request *req, int channels, const float *gdst, int64_t dst_stride, float *gsrc,
+                 int64_t src_stride, aai_layout *layout)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(req, 1, gdst, dst_stride, gsrc, src_stride, g));
-    AAI_TRY(require_device());
-    DeviceBuffer dGdst, dGsrc;
-    hipStream_t stream = nullptr;
-    AAI_HIP(dGdst.alloc(sizeof(float) * (size_t)g.dW * g.dH));
-    AAI_HIP(dGsrc.alloc(sizeof(float) * (size_t)g.W * g.H));
-    AAI_HIP(upload(dGdst, gdst, dst_stride, g.dW, g.dH, sizeof(float)));
-    AAI_TRY(run(*req, g, 1, dGdst.as<const float>(), g.dW, 0, dGsrc.as<float>(), g.W, 0, stream));
-    AAI_HIP(hipStreamSynchronize(stream));
-    AAI_HIP(download(gsrc, src_stride, dGsrc, g.W, g.H, sizeof(float)));
-    return finish(*req, g, layout);
-}
-
-typedef int (*AdjointInterleavedEnqueue)(const aai_request &, const aai::Geometry &, int, int, const float *, int64_t, int64_t, float *, int64_t, int64_t, hipStream_t);
-
-// aai_adjoint_interleaved_device_f32 / aai_adjoint_rotated_interleaved_device_f32
-int adjoint_interleaved_device(AdjointInterleavedEnqueue run, const aai_request *req, int32_t batch, int32_t channels, const float *d_gdst, int64_t dst_stride,
-                               int64_t dst_image_stride, float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
-{
-    aai::Geometry g;
-    AAI_TRY(check_adjoint_interleaved(req, batch, channels, d_gdst, dst_stride, d_gsrc, src_stride, g));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(run(*req, g, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
-}
-
-// aai_adjoint_interleaved_f32 / aai_adjoint_rotated_interleaved_f32: upload gdst, one launch on the null stream, download gsrc (dense rows of width x channels elements on the device)
-int adjoint_interleaved_host(AdjointInterleavedEnqueue run, const aai_request *req, int channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
-{
-    aai::Geometry g;
-    AAI_TRY(check_adjoint_interleaved(req, 1, channels, gdst, dst_stride, gsrc, src_stride, g));
+    AAI_TRY(check_adjoint(req, 1, interleaved, channels, gdst, dst_stride, gsrc, src_stride, g));
     AAI_TRY(require_device());
     const int64_t rowDst = (int64_t)g.dW * channels, rowSrc = (int64_t)g.W * channels;
     DeviceBuffer dGdst, dGsrc;
@@ -311,7 +285,7 @@ int adjoint_interleaved_host(AdjointInterleavedEnqueue run, const aai_request *r
     AAI_HIP(dGdst.alloc(sizeof(float) * (size_t)rowDst * g.dH));
     AAI_HIP(dGsrc.alloc(sizeof(float) * (size_t)rowSrc * g.H));
     AAI_HIP(upload(dGdst, gdst, dst_stride, rowDst, g.dH, sizeof(float)));
-    AAI_TRY(run(*req, g, 1, channels, dGdst.as<const float>(), rowDst, 0, dGsrc.as<float>(), rowSrc, 0, stream));
+    AAI_TRY(enqueue_adjoint(family, *req, g, 1, channels, dGdst.as<const float>(), rowDst, 0, dGsrc.as<float>(), rowSrc, 0, stream));
     AAI_HIP(hipStreamSynchronize(stream));
     AAI_HIP(download(gsrc, src_stride, dGsrc, rowSrc, g.H, sizeof(float)));
     return finish(*req, g, layout);
@@ -489,84 +463,66 @@ int aai_adjoint_batch_device_f32(const aai_request *req, int32_t batch,
                                  const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
                                  float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
-    return adjoint_device(enqueue_adjoint, req, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
+    return adjoint_device(ADJOINT_GENERAL, false, req, batch, 1, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
 }
 
 int aai_adjoint_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
 {
-    return adjoint_host(enqueue_adjoint, req, gdst, dst_stride, gsrc, src_stride, layout);
+    return adjoint_host(ADJOINT_GENERAL, false, req, 1, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
-int aai_adjoint_prepare(const aai_request *req)
-{
-    aai::Geometry g;
-    AAI_TRY(check_adjoint_request(req, 1, g));
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue_adjoint_planned(*req, g, 0, nullptr, 0, 0, nullptr, 0, 0, nullptr));
-    g_lastError.clear();
-    return AAI_OK;
-}
+int aai_adjoint_prepare(const aai_request *req) { return adjoint_prepare(ADJOINT_PLANNED, req); }
 
 int aai_adjoint_planned_batch_device_f32(const aai_request *req, int32_t batch,
                                          const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
                                          float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
-    return adjoint_device(enqueue_adjoint_planned, req, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
+    return adjoint_device(ADJOINT_PLANNED, false, req, batch, 1, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
 }
 
 int aai_adjoint_planned_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
 {
-    return adjoint_host(enqueue_adjoint_planned, req, gdst, dst_stride, gsrc, src_stride, layout);
+    return adjoint_host(ADJOINT_PLANNED, false, req, 1, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
-int aai_adjoint_rotated_prepare(const aai_request *req)
-{
-    aai::Geometry g;
-    AAI_TRY(check_adjoint_request(req, 1, g));
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue_adjoint_rotated(*req, g, 0, nullptr, 0, 0, nullptr, 0, 0, nullptr));
-    g_lastError.clear();
-    return AAI_OK;
-}
+int aai_adjoint_rotated_prepare(const aai_request *req) { return adjoint_prepare(ADJOINT_ROTATED, req); }
 
 int aai_adjoint_rotated_batch_device_f32(const aai_request *req, int32_t batch,
                                          const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
                                          float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
-    return adjoint_device(enqueue_adjoint_rotated, req, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
+    return adjoint_device(ADJOINT_ROTATED, false, req, batch, 1, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
 }
 
 int aai_adjoint_rotated_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
 {
-    return adjoint_host(enqueue_adjoint_rotated, req, gdst, dst_stride, gsrc, src_stride, layout);
+    return adjoint_host(ADJOINT_ROTATED, false, req, 1, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
 int aai_adjoint_interleaved_device_f32(const aai_request *req, int32_t batch, int32_t channels,
                                        const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
                                        float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
-    return adjoint_interleaved_device(enqueue_adjoint_interleaved, req, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride,
-                                      src_image_stride, stream);
+    return adjoint_device(ADJOINT_GENERAL, true, req, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
 }
 
 int aai_adjoint_interleaved_f32(const aai_request *req, int32_t channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride,
                                 aai_layout *layout)
 {
-    return adjoint_interleaved_host(enqueue_adjoint_interleaved, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
+    return adjoint_host(ADJOINT_GENERAL, true, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
 int aai_adjoint_rotated_interleaved_device_f32(const aai_request *req, int32_t batch, int32_t channels,
                                                const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
                                                float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
-    return adjoint_interleaved_device(enqueue_adjoint_rotated_interleaved, req, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride,
-                                      src_image_stride, stream);
+    return adjoint_device(ADJOINT_ROTATED, true, req, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
 }
 
 int aai_adjoint_rotated_interleaved_f32(const aai_request *req, int32_t channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride,
                                         aai_layout *layout)
 {
-    return adjoint_interleaved_host(enqueue_adjoint_rotated_interleaved, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
+    return adjoint_host(ADJOINT_ROTATED, true, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
 int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)

@@ -508,8 +508,6 @@ std::string plan_description(const aai_request &rq, int channels)
     return std::string();
 }
 
-constexpr int kMaxGridZ = 65535;
-
 // element offset into a typed source buffer
 static const void *src_at(const void *base, int srcType, int64_t elements)
 {
@@ -604,52 +602,30 @@ static int adjoint_scratch_pool(int device, hipMemPool_t *out)
     return AAI_OK;
 }
 
-// the two launches of the general adjoint on `stream`, chunk by chunk; channels == 1: aai_adjoint.hip, 2..4: aai_adjoint_multi.hip
-static int enqueue_adjoint_channels(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
-                                    int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+// The scratch and the chunk loop of every adjoint family: fp64 scratch of imageBytes per image in flight from the device's pool
+// (stream-ordered: hipMallocFromPoolAsync / hipFreeAsync on `stream`; imageBytes == 0: none, n == nullptr), the batch in chunks of
+// chunk_images(), and launch(nb, gd, gs, n) -> hipError_t for the nb images of a chunk at gd / gs.  A launch error is reported under
+// `name`, which the launchers may set; the scratch is freed whatever the launches returned.  aai_last_kernel(): name, "+listed" appended.
+template <typename Launch>
+static int for_each_adjoint_chunk(int batch, const float *dGdst, int64_t dstImageStride, float *dGsrc, int64_t srcImageStride, size_t imageBytes,
+                                  int device, hipStream_t stream, const char *&name, bool listed, Launch launch)
 {
-    // (AAI_POLICY_DOUBLE_PRECISION / AAI_POLICY_PREFER_CELL choose between forward kernels; the adjoint has one, in double precision)
-    const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
-    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
-    // scratch: one fp64 image of the dst size (times the channels) per image in flight; large batches go through in chunks of about 1 GiB of it
-    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * (size_t)channels * sizeof(double);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch, kMaxGridZ), ((size_t)1 << 30) / imageBytes));
-    int device = 0;
-    AAI_HIP(hipGetDevice(&device));
-    hipMemPool_t scratch = nullptr;
-    {
+    const int chunk = chunk_images(batch, imageBytes);
+    double *n = nullptr;
+    if (imageBytes) {
+        hipMemPool_t scratch = nullptr;
         const int rc = adjoint_scratch_pool(device, &scratch);
         if (rc != AAI_OK) return rc;
+        AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
     }
-    double *n = nullptr;
-    AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
-    const char *name = "";
     hipError_t e = hipSuccess;
-    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
-        const int nb = std::min(batch - b0, chunk);
-        const float *gd = dGdst + (int64_t)b0 * dstImageStride;
-        float *gs = dGsrc + (int64_t)b0 * srcImageStride;
-        e = channels == 1 ? aai::launch_adjoint(r, nb, gd, dv, n, gs, sv, stream, &name)
-                          : aai::launch_adjoint_multi(r, channels, nb, gd, dv, n, gs, sv, stream, &name);
-    }
-    const hipError_t ef = hipFreeAsync(n, stream);
-    g_lastKernel = name;
+    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk)
+        e = launch(std::min(batch - b0, chunk), dGdst + (int64_t)b0 * dstImageStride, dGsrc + (int64_t)b0 * srcImageStride, n);
+    const hipError_t ef = n ? hipFreeAsync(n, stream) : hipSuccess;
+    g_lastKernel = listed ? std::string(name) + "+listed" : std::string(name);
     if (e != hipSuccess) return hip_fail(e, name);
     if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     return AAI_OK;
-}
-
-int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
-                    float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
-{
-    return enqueue_adjoint_channels(rq, g, batch, 1, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
-}
-
-int enqueue_adjoint_interleaved(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
-                                int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
-{
-    if (channels == 1) return enqueue_adjoint(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
-    return enqueue_adjoint_channels(rq, g, batch, channels, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
 }
 
 // The adjoint tables of an axis plan (Plan::adjState): the inverse ranges of its two tables and, where it has flagged pixels, the
@@ -701,61 +677,6 @@ static int build_adjoint_tables(Plan &p)
     }
     p.adjSrcCount = (unsigned)src2.size(); p.adjDstCount = (unsigned)dst2.size();
     p.adjState = 1;
-    return AAI_OK;
-}
-
-int enqueue_adjoint_planned(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
-                            float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
-{
-    const bool prepareOnly = dGdst == nullptr;
-    PlanRef p;
-    if (pick_kernel(rq, g) == AAI_KERNEL_AXIS) {
-        // the forward's plan under the forward's key (a packed fp32 image, one channel, the whole image)
-        const int rc = acquire_plan(rq, g, -1, -1, 1, aai::ROT_FORM_QUAD, &p, /*onCallerStream*/ !prepareOnly, stream);
-        if (rc != AAI_OK) return rc;
-        std::lock_guard<std::mutex> lock(p->build);
-        const int rt = build_adjoint_tables(*p);
-        if (rt != AAI_OK) return rt;
-        if (p->adjState != 1) p.reset();
-    }
-    if (prepareOnly) return AAI_OK;
-    if (!p) return enqueue_adjoint(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
-
-    std::lock_guard<std::mutex> lock(p->launch);
-    const aai::AxisLaunch f = make_axis_launch(*p, 1, dstStride);
-    aai::AxisAdjointLaunch a{};
-    a.laneTab = p->dLane; a.rowTab = p->dRow; a.colRange = p->dColRange; a.rowRange = p->dRowRange;
-    a.srcW = g.W; a.srcH = g.H;
-    a.outBase = f.outBase; a.outStrideA = f.outStrideA; a.outStrideB = f.outStrideB;
-    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
-    const bool listed = p->adjSrcCount != 0 && p->adjDstCount != 0;
-    g_lastKernel = listed ? "aai_axis_adjoint_kernel+listed" : "aai_axis_adjoint_kernel";
-    // the correction pass's scratch: one fp64 image of the dst size per image in flight, as in enqueue_adjoint -- only where there is a list
-    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * sizeof(double);
-    int chunk = std::min(batch, kMaxGridZ);
-    double *n = nullptr;
-    aai::RotLaunch r{};
-    if (listed) {
-        r = aai::make_rot_launch(g, rq.mode, rq.policy);
-        chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk, ((size_t)1 << 30) / imageBytes));
-        hipMemPool_t scratch = nullptr;
-        const int rc = adjoint_scratch_pool(p->device, &scratch);
-        if (rc != AAI_OK) return rc;
-        AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
-    }
-    hipError_t e = hipSuccess;
-    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
-        const int nb = std::min(batch - b0, chunk);
-        const float *gd = dGdst + (int64_t)b0 * dstImageStride;
-        float *gs = dGsrc + (int64_t)b0 * srcImageStride;
-        e = aai::launch_axis_adjoint(a, nb, gd, dv, gs, sv, stream, nullptr);
-        if (e == hipSuccess && listed)
-            e = aai::launch_adjoint_listed(r, nb, gd, dv, n, gs, sv, static_cast<const uint2 *>(p->dAdjDstList), p->adjDstCount,
-                                           static_cast<const uint2 *>(p->dAdjSrcList), p->adjSrcCount, stream);
-    }
-    const hipError_t ef = n ? hipFreeAsync(n, stream) : hipSuccess;
-    if (e != hipSuccess) return hip_fail(e, "aai_axis_adjoint_kernel");
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     return AAI_OK;
 }
 
@@ -832,104 +753,83 @@ static int build_rot_adjoint_tables(Plan &p)
     return AAI_OK;
 }
 
-int enqueue_adjoint_rotated(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
-                            float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+// the forward's single-channel plan (the forward's key: a packed fp32 image, the whole image) with its rotated-adjoint tables, which
+// do not depend on the channel count: every channel count shares them
+static int acquire_rot_adjoint_plan(const aai_request &rq, const Geometry &g, bool prepareOnly, hipStream_t stream, PlanRef *out)
 {
-    const int kernel = pick_kernel(rq, g);
-    if (kernel != AAI_KERNEL_ROTATED && kernel != AAI_KERNEL_FAST)      // reduced angle 0: one entry serves every rotation
-        return enqueue_adjoint_planned(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
-    const bool prepareOnly = dGdst == nullptr;
-    PlanRef p;
-    {
-        // the forward's plan under the forward's key (a packed fp32 image, one channel, the whole image)
-        const int rc = acquire_plan(rq, g, -1, -1, 1, rot_form(rq, g, 1, aai::SRC_F32, g.W), &p, /*onCallerStream*/ !prepareOnly, stream);
-        if (rc != AAI_OK) return rc;
-        std::lock_guard<std::mutex> lock(p->build);
-        const int rt = build_rot_adjoint_tables(*p);
-        if (rt != AAI_OK) return rt;
-    }
-    if (prepareOnly) return AAI_OK;
-    if (p->rotAdjState != 1) return enqueue_adjoint(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
-
-    std::lock_guard<std::mutex> lock(p->launch);
-    const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
-    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
-    // scratch: one fp64 image of the dst size per image in flight, chunked as in enqueue_adjoint
-    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * sizeof(double);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch, kMaxGridZ), ((size_t)1 << 30) / imageBytes));
-    hipMemPool_t scratch = nullptr;
-    {
-        const int rc = adjoint_scratch_pool(p->device, &scratch);
-        if (rc != AAI_OK) return rc;
-    }
-    double *n = nullptr;
-    AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
-    const char *name = "";
-    const bool listed = p->adjSrcCount != 0;
-    hipError_t e = hipSuccess;
-    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
-        const int nb = std::min(batch - b0, chunk);
-        const float *gd = dGdst + (int64_t)b0 * dstImageStride;
-        float *gs = dGsrc + (int64_t)b0 * srcImageStride;
-        e = aai::launch_adjoint_plain(r, nb, gd, dv, p->dAdjSums, n, gs, sv, stream, &name);
-        if (e == hipSuccess && listed)
-            e = aai::launch_adjoint_gather_listed(r, nb, n, gs, sv, static_cast<const uint2 *>(p->dAdjSrcList), p->adjSrcCount, stream);
-    }
-    const hipError_t ef = hipFreeAsync(n, stream);
-    g_lastKernel = listed ? std::string(name) + "+listed" : std::string(name);
-    if (e != hipSuccess) return hip_fail(e, name);
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    return AAI_OK;
+    const int rc = acquire_plan(rq, g, -1, -1, 1, rot_form(rq, g, 1, aai::SRC_F32, g.W), out, /*onCallerStream*/ !prepareOnly, stream);
+    if (rc != AAI_OK) return rc;
+    std::lock_guard<std::mutex> lock((*out)->build);
+    return build_rot_adjoint_tables(**out);
 }
 
-int enqueue_adjoint_rotated_interleaved(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
-                                        int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
+                    int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
 {
-    if (channels == 1) return enqueue_adjoint_rotated(rq, g, batch, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+    const bool prepareOnly = dGdst == nullptr;
+    // ---- the routing table (aai_engine.hpp): what the entry asked for -> the family whose launches serve the call
     const int kernel = pick_kernel(rq, g);
-    if (kernel != AAI_KERNEL_ROTATED && kernel != AAI_KERNEL_FAST)      // reduced angle 0: there is no interleaved transposed separable kernel
-        return enqueue_adjoint_interleaved(rq, g, batch, channels, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
+    if (family == ADJOINT_ROTATED && kernel != AAI_KERNEL_ROTATED && kernel != AAI_KERNEL_FAST)      // reduced angle 0
+        family = channels == 1 ? ADJOINT_PLANNED : ADJOINT_GENERAL;
+    if (family == ADJOINT_PLANNED && (kernel != AAI_KERNEL_AXIS || channels != 1)) family = ADJOINT_GENERAL;
     PlanRef p;
-    {
-        // the plan enqueue_adjoint_rotated acquires -- the forward's SINGLE-channel plan under the forward's key: S and the source list
-        // do not depend on the channel count, so they are shared with single-channel calls
-        const int rc = acquire_plan(rq, g, -1, -1, 1, rot_form(rq, g, 1, aai::SRC_F32, g.W), &p, /*onCallerStream*/ true, stream);
+    if (family == ADJOINT_PLANNED) {
+        // the forward's plan under the forward's key (a packed fp32 image, one channel, the whole image)
+        const int rc = acquire_plan(rq, g, -1, -1, 1, aai::ROT_FORM_QUAD, &p, /*onCallerStream*/ !prepareOnly, stream);
         if (rc != AAI_OK) return rc;
         std::lock_guard<std::mutex> lock(p->build);
-        const int rt = build_rot_adjoint_tables(*p);
+        const int rt = build_adjoint_tables(*p);
         if (rt != AAI_OK) return rt;
-    }
-    if (p->rotAdjState != 1)
-        return enqueue_adjoint_interleaved(rq, g, batch, channels, dGdst, dstStride, dstImageStride, dGsrc, srcStride, srcImageStride, stream);
-
-    std::lock_guard<std::mutex> lock(p->launch);
-    const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
-    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
-    // scratch: one fp64 image of the dst size times the channels per image in flight, chunked as in enqueue_adjoint_channels
-    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * (size_t)channels * sizeof(double);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch, kMaxGridZ), ((size_t)1 << 30) / imageBytes));
-    hipMemPool_t scratch = nullptr;
-    {
-        const int rc = adjoint_scratch_pool(p->device, &scratch);
+        if (p->adjState != 1) family = ADJOINT_GENERAL;          // a wide or dense plan, tables the inversion refuses
+    } else if (family == ADJOINT_ROTATED) {
+        const int rc = acquire_rot_adjoint_plan(rq, g, prepareOnly, stream, &p);
         if (rc != AAI_OK) return rc;
+        if (p->rotAdjState != 1) family = ADJOINT_GENERAL;       // rotAdjState 2
     }
-    double *n = nullptr;
-    AAI_HIP(hipMallocFromPoolAsync((void **)&n, imageBytes * (size_t)chunk, scratch, stream));
+    if (prepareOnly) return AAI_OK;
+
+    // ---- the launches.  A plan's launches are serialised between caller threads; the general family has no plan.
+    int device = 0;
+    std::unique_lock<std::mutex> lock;
+    if (family == ADJOINT_GENERAL) AAI_HIP(hipGetDevice(&device));
+    else { device = p->device; lock = std::unique_lock<std::mutex>(p->launch); }
+    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
+    // scratch: one fp64 image of the dst size times the channels per image in flight
+    size_t imageBytes = (size_t)g.dW * (size_t)g.dH * (size_t)channels * sizeof(double);
     const char *name = "";
-    const bool listed = p->adjSrcCount != 0;
-    hipError_t e = hipSuccess;
-    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
-        const int nb = std::min(batch - b0, chunk);
-        const float *gd = dGdst + (int64_t)b0 * dstImageStride;
-        float *gs = dGsrc + (int64_t)b0 * srcImageStride;
-        e = aai::launch_adjoint_plain_multi(r, channels, nb, gd, dv, p->dAdjSums, n, gs, sv, static_cast<const uint2 *>(p->dAdjSrcList), p->adjSrcCount,
-                                            stream, &name);
-    }
-    const hipError_t ef = hipFreeAsync(n, stream);
-    g_lastKernel = listed ? std::string(name) + "+listed" : std::string(name);
-    if (e != hipSuccess) return hip_fail(e, name);
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    return AAI_OK;
+    bool listed = false;                 // the plan has lists for a pass of the general kernels behind its own
+    aai::AxisAdjointLaunch a{};
+    if (family == ADJOINT_PLANNED) {
+        const aai::AxisLaunch f = make_axis_launch(*p, 1, dstStride);
+        a.laneTab = p->dLane; a.rowTab = p->dRow; a.colRange = p->dColRange; a.rowRange = p->dRowRange;
+        a.srcW = g.W; a.srcH = g.H;
+        a.outBase = f.outBase; a.outStrideA = f.outStrideA; a.outStrideB = f.outStrideB;
+        name = "aai_axis_adjoint_kernel";
+        listed = p->adjSrcCount != 0 && p->adjDstCount != 0;
+        if (!listed) imageBytes = 0;     // the transposed separable kernel needs no scratch, only the correction pass does
+    } else if (family == ADJOINT_ROTATED) listed = p->adjSrcCount != 0;
+    // (AAI_POLICY_DOUBLE_PRECISION / AAI_POLICY_PREFER_CELL choose between forward kernels; the adjoint has one, in double precision)
+    const aai::RotLaunch r = family != ADJOINT_PLANNED || listed ? aai::make_rot_launch(g, rq.mode, rq.policy) : aai::RotLaunch{};
+    const uint2 *srcList = p ? static_cast<const uint2 *>(p->dAdjSrcList) : nullptr, *dstList = p ? static_cast<const uint2 *>(p->dAdjDstList) : nullptr;
+    auto launch = [&](int nb, const float *gd, float *gs, double *n) -> hipError_t {
+        hipError_t e = hipSuccess;
+        switch (family) {
+        case ADJOINT_GENERAL:
+            return channels == 1 ? aai::launch_adjoint(r, nb, gd, dv, n, gs, sv, stream, &name)
+                                 : aai::launch_adjoint_multi(r, channels, nb, gd, dv, n, gs, sv, stream, &name);
+        case ADJOINT_PLANNED:
+            e = aai::launch_axis_adjoint(a, nb, gd, dv, gs, sv, stream, nullptr);
+            if (e == hipSuccess && listed) e = aai::launch_adjoint_listed(r, nb, gd, dv, n, gs, sv, dstList, p->adjDstCount, srcList, p->adjSrcCount, stream);
+            return e;
+        case ADJOINT_ROTATED:
+            if (channels != 1) return aai::launch_adjoint_plain_multi(r, channels, nb, gd, dv, p->dAdjSums, n, gs, sv, srcList, p->adjSrcCount, stream, &name);
+            e = aai::launch_adjoint_plain(r, nb, gd, dv, p->dAdjSums, n, gs, sv, stream, &name);
+            if (e == hipSuccess && listed) e = aai::launch_adjoint_gather_listed(r, nb, n, gs, sv, srcList, p->adjSrcCount, stream);
+            return e;
+        }
+        return e;
+    };
+    return for_each_adjoint_chunk(batch, dGdst, dstImageStride, dGsrc, srcImageStride, imageBytes, device, stream, name, listed, launch);
 }
 
 int require_device()

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <list>
 #include <memory>
@@ -110,7 +112,7 @@ struct DevicePool {
     hipEvent_t fork[kSideSlots] = {}, join[kSideSlots] = {};
     bool sideReady = false, sideFailed = false;
     unsigned besideLaunches = 0, nextSide = 0;
-    // the adjoint's scratch (enqueue_adjoint): a memory pool of the library's own, created on the first adjoint call of the device.
+    // the adjoint's scratch (for_each_adjoint_chunk behind enqueue_adjoint): a memory pool of the library's own, created on the first adjoint call of the device.
     // It keeps what it has been given (release threshold: everything), so that after the first call of a size an allocation is
     // stream-ordered bookkeeping and never a trip to the driver -- the device's default pool hands its memory back at every
     // synchronisation.  aai_shutdown destroys it.
@@ -132,21 +134,6 @@ int resolved_kernel(const aai_request &rq, const Geometry &g);      // pick_kern
 void fill_layout(const Geometry &g, int kernel, aai_layout *out);
 int require_device();
 
-// The planned adjoint (aai_adjoint_planned_*; the caller has checked the arguments).  Axis-aligned requests whose plan is neither
-// wide nor dense: the forward's plan (looked up with the forward's key, built like aai_prepare builds it when missing) with its
-// adjoint tables (built on first need: blocks), then aai_axis_adjoint_kernel and, where the plan has flagged pixels, the listed
-// passes of the general adjoint behind it.  Every other request: enqueue_adjoint.  dGdst == NULL: prepare only (aai_adjoint_prepare).
-int enqueue_adjoint_planned(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
-                            float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
-
-// The planned adjoint at every rotation (aai_adjoint_rotated_*; the caller has checked the arguments).  Reduced angle 0:
-// enqueue_adjoint_planned.  Otherwise the forward's plan (looked up with the forward's key, built like aai_prepare(req, 1) builds it when
-// missing) with its sums and knife lists (built on first need: blocks), then the element-wise pass 1, the plain gather and, where the
-// plan lists source pixels, the listed gather of the general adjoint behind it.  A plan in rotAdjState 2: enqueue_adjoint.
-// dGdst == NULL: prepare only (aai_adjoint_rotated_prepare).
-int enqueue_adjoint_rotated(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
-                            float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
-
 // Finds the plan for (request, current device) or inserts a fresh one, then builds it if nobody has (blocking: table
 // uploads, the one-off scans, K1's launch-shape measurement -- on `stream` when the caller has one to give (onCallerStream; a
 // stream that is being captured into a graph is not used), else on the device pool's build stream).
@@ -164,29 +151,52 @@ int enqueue(const aai_request &rq, const Geometry &g, int batch, const void *dSr
             float *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream, int band0 = -1, int band1 = -1,
             int channels = 1);
 
-// The adjoint of an area / fast request (the caller has checked the arguments): the two launches on `stream`, with stream-ordered scratch from the device pool's memory pool (hipMallocFromPoolAsync /
-// hipFreeAsync on `stream`): no plan, nothing blocks.  Strides in elements.
-int enqueue_adjoint(const aai_request &rq, const Geometry &g, int batch, const float *dGdst, int64_t dstStride, int64_t dstImageStride,
-                    float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
+// grid.z carries the batch of a launch
+constexpr int kMaxGridZ = 65535;
 
-// The adjoint of images with `channels` = 1..4 interleaved channels (aai_adjoint_interleaved_*; the caller has checked the arguments).
-// One channel: enqueue_adjoint, identical bits.  Otherwise the channel-aware kernels (aai_adjoint_multi.hip) with scratch of
-// dW x dH x channels doubles per image in flight from the same pool, the chunk sized from that; only enqueues, never synchronises.
-// Element (x, y, c) of image b at b * imageStride + y * stride + x * channels + c.
-int enqueue_adjoint_interleaved(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
-                                int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
+// How many images of a batch the adjoint takes per round of launches: all that grid.z carries, cut so that their fp64 scratch of
+// imageBytes each stays within 1 GiB (imageBytes == 0: the launches need no scratch); at least one.
+inline int chunk_images(int batch, size_t imageBytes)
+{
+    size_t chunk = (size_t)std::max(0, std::min(batch, kMaxGridZ));
+    if (imageBytes) chunk = std::min(chunk, ((size_t)1 << 30) / imageBytes);
+    return (int)std::max<size_t>(1, chunk);
+}
 
-// The planned adjoint at general rotations for `channels` = 1..4 interleaved channels (aai_adjoint_rotated_interleaved_*; the caller has
-// checked the arguments).  One channel: enqueue_adjoint_rotated, identical bits.  Reduced angle 0: enqueue_adjoint_interleaved, the
-// GENERAL interleaved adjoint with its bits -- an interleaved transposed separable kernel is out of scope (the single-channel entry
-// differs there: it forwards to the fp32 axis kernel).  Otherwise the plan enqueue_adjoint_rotated acquires (the forward's
-// single-channel plan, same key, its tables built on first need: blocks; S and the source list are shared with single-channel calls,
-// no second copy and no new per-plan memory), then per chunk the element-wise pass 1, the plain gather with `channels` accumulators
-// and, where the plan lists source pixels, the general multi-channel gather over them (aai_adjoint_plain_multi.hip).  A plan in
-// rotAdjState 2: enqueue_adjoint_interleaved.  Scratch of dW x dH x channels doubles per image in flight, the chunk sized from that as
-// in enqueue_adjoint_interleaved.  Only enqueues once the tables exist.
-int enqueue_adjoint_rotated_interleaved(const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
-                                        int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
+// The adjoint of an area / fast request, every entry's (aai_adjoint_*; the caller has checked the arguments): gsrc = W^T gdst for
+// `batch` images of `channels` = 1..4 interleaved channels, element (x, y, c) of image b at b * imageStride + y * stride + x * channels
+// + c, strides in elements.  `family` is what the entry asks for; which launches serve the call:
+//
+//   asked for   request / plan                                      served by
+//   GENERAL     any                                                 GENERAL
+//   PLANNED     not axis-aligned (or channels != 1)                 GENERAL
+//               axis plan that is wide or dense, tables the         GENERAL
+//               inversion refuses, lists over most of the image
+//               (adjState 2)
+//               axis plan with its adjoint tables (adjState 1)      PLANNED
+//   ROTATED     reduced angle 0, one channel                        as PLANNED above
+//               reduced angle 0, 2..4 channels                      GENERAL (there is no interleaved transposed separable kernel)
+//               plan that keeps the general adjoint (rotAdjState 2) GENERAL
+//               plan with its sums (rotAdjState 1)                  ROTATED
+//
+//   GENERAL  no plan, nothing blocks: pass 1 and the gather of aai_adjoint.hip (one channel) or aai_adjoint_multi.hip (2..4; a pair's
+//            weight computed once, channel c with the bits of plane c alone), fp64.
+//   PLANNED  the forward's plan (the forward's key, built like aai_prepare builds it when missing) with its adjoint tables, then
+//            aai_axis_adjoint_kernel (fp32, no scratch) and, where the plan has lists, the listed passes of the general adjoint behind
+//            it: "aai_axis_adjoint_kernel+listed".
+//   ROTATED  the forward's SINGLE-channel plan (same key; built like aai_prepare(req, 1) builds it) with its sums and source list, which
+//            every channel count shares, then the element-wise pass 1 and the plain gather (aai_adjoint_plain.hip, or
+//            aai_adjoint_plain_multi.hip with `channels` accumulators) and, where the plan lists source pixels, the general gather over
+//            them: "<plain name>+listed".  The general adjoint's bits.
+//
+// A plan's tables are built on first need, under its `build` lock: that blocks; afterwards a call only enqueues.  The launches of
+// PLANNED and ROTATED hold the plan's `launch` lock; GENERAL takes none.  Scratch: dW x dH x channels doubles per image in flight
+// (PLANNED: dW x dH where there are lists, else none), stream-ordered from the device pool's memory pool (hipMallocFromPoolAsync /
+// hipFreeAsync on `stream`), the batch in chunks of chunk_images().
+// dGdst == NULL: prepare only -- build what the family needs and return (aai_adjoint_prepare, aai_adjoint_rotated_prepare).
+enum AdjointFamily { ADJOINT_GENERAL, ADJOINT_PLANNED, ADJOINT_ROTATED };
+int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
+                    int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 
 }  // namespace engine
 }  // namespace aai

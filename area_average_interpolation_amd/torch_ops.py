@@ -27,41 +27,32 @@ def _ensure_prepared(rq, channels=1):
     api.prepare(rq, channels)
 
 
-def _ensure_adjoint_prepared(rq):
-    """The planned adjoint's first call per (geometry, device) builds the plan's adjoint tables and synchronises
-    (aai_adjoint_prepare): do that in the forward, outside any stream capture.  Only a separable (kernel=1), non-dense plan can
-    hold such tables; every other plan's backward runs the general kernels, which need none."""
-    tokens = api.plan_shape(rq).split()
-    if "kernel=%d" % L.KERNEL_AXIS not in tokens or "dense=0" not in tokens or "adjoint=none" not in tokens:
+# route of resample()'s backward -> (tokens of api.plan_shape(rq) -> are the plan's adjoint tables still to be built?, what builds them,
+# planned_backward as the message shows it)
+#   planned      planned_backward=True, or "any" at a multiple of 90 degrees: only a separable (kernel=1), non-dense plan can hold such tables;
+#                every other plan's backward runs the general kernels, which need none
+#   rotated      "any" at a general rotation: the plan's sums and knife lists
+#   interleaved  the tables of aai_adjoint_rotated_interleaved_device_f32 live on the SINGLE-channel plan of the geometry, which the
+#                interleaved forward (prepared for C channels) does not build: aai_adjoint_rotated_prepare builds both
+_ADJOINT_TABLES = {
+    "planned": (lambda t: "kernel=%d" % L.KERNEL_AXIS in t and "dense=0" in t and "adjoint=none" in t, api.adjoint_prepare, "True"),
+    "rotated": (lambda t: "rot_adjoint=none" in t, api.adjoint_rotated_prepare, '"any"'),
+    "interleaved": (lambda t: not t or "rot_adjoint=none" in t, api.adjoint_rotated_prepare, '"interleaved"'),
+}
+
+
+def _ensure_adjoint_prepared(rq, route):
+    """The first call of a planned adjoint per (geometry, device) builds the plan's adjoint tables and synchronises (aai_adjoint_prepare,
+    aai_adjoint_rotated_prepare): do that in the forward, outside any stream capture.  Inside a capture missing tables are an error,
+    not a hidden synchronisation."""
+    missing, prepare, shown = _ADJOINT_TABLES[route]
+    if not missing(api.plan_shape(rq).split()):
         return
     if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("resample(planned_backward=True): this geometry has no adjoint tables on this device yet and the current "
-                           "stream is being captured; call resample() (or adjoint_prepare()) once with the same geometry before capturing")
-    api.adjoint_prepare(rq)
-
-
-def _ensure_rotated_adjoint_prepared(rq):
-    """planned_backward="any" at a general rotation: the first call of aai_adjoint_rotated_batch_device_f32 per (geometry, device) builds
-    the plan's sums and knife lists and synchronises (aai_adjoint_rotated_prepare): do that in the forward, outside any stream capture."""
-    if "rot_adjoint=none" not in api.plan_shape(rq).split():
-        return
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError('resample(planned_backward="any"): this geometry has no adjoint tables on this device yet and the current '
-                           "stream is being captured; call resample() (or adjoint_rotated_prepare()) once with the same geometry before capturing")
-    api.adjoint_rotated_prepare(rq)
-
-
-def _ensure_interleaved_adjoint_prepared(rq):
-    """planned_backward="interleaved" on the interleaved route: the tables of aai_adjoint_rotated_interleaved_device_f32 live on the
-    SINGLE-channel plan of the geometry, which the interleaved forward (prepared for C channels) does not build.  Build both
-    (aai_adjoint_rotated_prepare) in the forward, outside any stream capture."""
-    tokens = api.plan_shape(rq).split()
-    if tokens and "rot_adjoint=none" not in tokens:
-        return
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError('resample(planned_backward="interleaved"): this geometry has no adjoint tables on this device yet and the current '
-                           "stream is being captured; call resample() (or adjoint_rotated_prepare()) once with the same geometry before capturing")
-    api.adjoint_rotated_prepare(rq)
+        raise RuntimeError("resample(planned_backward=%s): this geometry has no adjoint tables on this device yet and the current "
+                           "stream is being captured; call resample() (or %s()) once with the same geometry before capturing"
+                           % (shown, prepare.__name__))
+    prepare(rq)
 
 
 def _normalise_planned(planned_backward):
@@ -83,10 +74,7 @@ class _Resample(torch.autograd.Function):
             with torch.cuda.device(x.device):
                 _ensure_prepared(rq)
                 if planned and ctx.needs_input_grad[0]:
-                    if planned == "any" and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST):
-                        _ensure_rotated_adjoint_prepared(rq)
-                    else:
-                        _ensure_adjoint_prepared(rq)
+                    _ensure_adjoint_prepared(rq, "rotated" if planned == "any" and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST) else "planned")
                 api.resample_device(rq, x.data_ptr(), W, y.data_ptr(), lay.dst_width, stream=torch.cuda.current_stream().cuda_stream,
                                     batch=B, src_image_stride=H * W, dst_image_stride=lay.dst_height * lay.dst_width)
         return y
@@ -120,7 +108,7 @@ class _ResampleInterleaved(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _ensure_prepared(rq, C)
             if planned and ctx.needs_input_grad[0]:
-                _ensure_interleaved_adjoint_prepared(rq)
+                _ensure_adjoint_prepared(rq, "interleaved")
             api.resample_interleaved_device(rq, C, x.data_ptr(), W * C, y.data_ptr(), dW * C, stream=torch.cuda.current_stream().cuda_stream,
                                             batch=B, src_image_stride=H * W * C, dst_image_stride=dH * dW * C)
         return y

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY -- serial CPU replay of the planned adjoint at general rotations (aai_adjoint_rotated_*: csrc/aai_engine.cpp
-// build_rot_adjoint_tables / enqueue_adjoint_rotated, csrc/aai_adjoint_plain.hip).
+// build_rot_adjoint_tables / enqueue_adjoint, the ROTATED family; csrc/aai_adjoint_plain.hip).
 //
 // Built by tests/test_adjoint_rotated_host.py with plain g++ (no HIP, no contraction) into tests/_build/libaai_adjplainemu.so.  It
 // reuses the PRODUCT's host planner (csrc/aai_plan.cpp: build_adjoint_lists) and the PRODUCT's per-pixel bodies

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY -- serial CPU replay of the interleaved planned adjoint at general rotations
-// (aai_adjoint_rotated_interleaved_*: csrc/aai_engine.cpp enqueue_adjoint_rotated_interleaved, csrc/aai_adjoint_plain_multi.hip).
+// (aai_adjoint_rotated_interleaved_*: csrc/aai_engine.cpp enqueue_adjoint, the ROTATED family with 2..4 channels; csrc/aai_adjoint_plain_multi.hip).
 //
 // Built by tests/test_adjoint_rotated_interleaved_host.py with plain g++ (no HIP, no contraction) into
 // tests/_build/libaai_adjplainmultiemu.so.  Like adjoint_plain_emulation.cpp it reuses the PRODUCT's host planner (csrc/aai_plan.cpp:

@@ -264,6 +264,78 @@ def test_planned_adjoint_is_deterministic_and_batches_match_single_images(gpu):
     assert seen == {False, True}
 
 
+def _batch_against_single_images(gpu, rq, batch, images, planned=True, seed=9):
+    """one planned call over `batch` dense images (gsrc prefilled with -7) and, for `images`, their single-image calls: bit for bit;
+    (gsrc of the batch, aai_last_kernel() of the batch call, gdst)"""
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    W, H = rq.src_width, rq.src_height
+    lay = gpu.query(rq)[2]
+    dW, dH = lay.dst_width, lay.dst_height
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    gd = torch.rand((batch, dH, dW), dtype=torch.float32, device="cuda", generator=gen)
+    gs = torch.full((batch, H, W), -7.0, dtype=torch.float32, device="cuda")
+    gpu.adjoint_device(rq, gd.data_ptr(), dW, gs.data_ptr(), W, st, batch=batch, dst_image_stride=dW * dH, src_image_stride=W * H, planned=planned)
+    torch.cuda.synchronize()
+    kernel = gpu.last_kernel()
+    for b in images:
+        one = torch.full((H, W), -1.0, dtype=torch.float32, device="cuda")
+        gpu.adjoint_device(rq, gd[b].data_ptr(), dW, one.data_ptr(), W, st, planned=planned)
+        torch.cuda.synchronize()
+        assert gpu.last_kernel() == kernel and torch.equal(gs[b], one), (b, kernel, gpu.last_kernel())
+    return gs, kernel, gd
+
+
+GRID_Z = 65535                                     # images one launch takes: grid.z carries the batch
+KNIFE_X2 = (264, 133, 3.0, 1.0, (12.5, 4.0))       # KNIFE at twice the size: the same edges through pixel centres, 88 x 44 dst pixels
+
+
+@pytest.mark.parametrize("geo", [KNIFE, KNIFE_X2], ids=["knife-grid.z-cut", "knife-x2-1GiB-cut"])
+def test_planned_adjoint_with_a_list_across_a_scratch_chunk_cut(gpu, geo):
+    """The planned path WITH a correction list takes fp64 scratch of dW x dH x 8 bytes per image in flight and goes through in chunks of
+    min(batch, 65535, 2^30 // per_image) images.  KNIFE_X2 (30,976 bytes per image) is cut by the 1 GiB rule, 1 < chunk < 65535, as in
+    test_rotated_adjoint_batch_of_two_scratch_chunks; KNIFE itself (44 x 22 dst pixels, 7,744 bytes per image: 2^30 // 7744 = 138,654)
+    is cut by grid.z first.  Three images past the cut: the images on both sides of it equal their single-image calls bit for bit."""
+    import torch
+    rq = _request(gpu, geo, 180.0, gpu.MODE_AREA)
+    lay = gpu.query(rq)[2]
+    per_image = lay.dst_width * lay.dst_height * 8
+    chunk = (1 << 30) // per_image
+    if geo is KNIFE_X2:
+        assert 1 < chunk < GRID_Z
+    else:
+        assert chunk > GRID_Z
+        chunk = GRID_Z
+    batch = chunk + 3
+    gs, kernel, gd = _batch_against_single_images(gpu, rq, batch, (0, chunk - 1, chunk, chunk + 1, batch - 1))
+    print("%s: %d bytes of scratch per image, chunk %d, batch %d, %.2f GB of gdst, %s" % (geo[:2], per_image, chunk, batch, gd.numel() * 4 / 1e9, gpu.plan_shape(rq)))
+    assert _flagged(gpu, rq)[0] > 0 and kernel == AXIS_KERNEL + "+listed", (kernel, gpu.plan_shape(rq))
+    assert bool((gs >= 0.0).all())                 # every pixel of every image written (weights and gradients are non-negative)
+    del gs, gd
+    torch.cuda.empty_cache()
+
+
+def test_planned_adjoint_without_scratch_past_grid_z(gpu):
+    """the planned path WITHOUT a list allocates nothing and is cut by grid.z alone: 65,540 images of 24 x 24 (4:1, 0 degrees; the first
+    geometry of MATRIX whose call reports no "+listed")"""
+    import torch
+    for W, H, sr, dr, ang, off, absolute in MATRIX:
+        rq = gpu.make_request(W, H, sr, dr, off if absolute else ((W - 1) / 2 + off[0], (H - 1) / 2 + off[1]), ang)
+        lay = gpu.query(rq)[2]
+        if _planned(gpu, rq, np.ones((lay.dst_height, lay.dst_width), np.float32))[1] == AXIS_KERNEL:
+            break
+    else:
+        pytest.fail("no geometry of MATRIX is served without the correction pass")
+    batch = 65540
+    # tiny images: if this path took scratch, the 1 GiB rule would not cut before grid.z either
+    assert batch > GRID_Z and (1 << 30) // (lay.dst_width * lay.dst_height * 8) > batch
+    gs, kernel, gd = _batch_against_single_images(gpu, rq, batch, (0, GRID_Z - 1, GRID_Z, GRID_Z + 1, batch - 1))
+    assert kernel == AXIS_KERNEL, (kernel, gpu.plan_shape(rq))
+    assert bool((gs >= 0.0).all())
+    del gs, gd
+    torch.cuda.empty_cache()
+
+
 @pytest.mark.parametrize("ang", [0.0, 90.0, 180.0, 270.0])
 def test_planned_adjoint_stays_inside_its_buffers(gpu, ang):
     """gdst is the guarded SOURCE (NaN around it), gsrc the guarded destination (sentinel everywhere), the three layouts of

@@ -314,6 +314,36 @@ def test_rotated_adjoint_batch_of_two_scratch_chunks(gpu):
     torch.cuda.empty_cache()
 
 
+def test_rotated_adjoint_past_grid_z(gpu):
+    """the sums path is cut by grid.z where the images are tiny: 65,540 images of 12 x 10 (2:1, 17.5 degrees; 7 x 7 dst pixels, 392 bytes of
+    scratch each, so the 1 GiB rule does not cut first).  The images on both sides of the cut equal their single-image calls and the
+    general adjoint's, bit for bit."""
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    W, H = 12, 10
+    rq = gpu.make_request(W, H, 2.0, 1.0, ((W - 1) / 2, (H - 1) / 2), 17.5)
+    lay = gpu.query(rq)[2]
+    dW, dH = lay.dst_width, lay.dst_height
+    batch, cut = 65540, 65535
+    assert batch > cut and (1 << 30) // (dW * dH * 8) > batch
+    gen = torch.Generator(device="cuda").manual_seed(9)
+    gd = torch.rand((batch, dH, dW), dtype=torch.float32, device="cuda", generator=gen)
+    outs = []
+    for planned in ("any", False):
+        gs = torch.full((batch, H, W), -7.0, dtype=torch.float32, device="cuda")
+        gpu.adjoint_device(rq, gd.data_ptr(), dW, gs.data_ptr(), W, st, batch=batch, dst_image_stride=dW * dH, src_image_stride=W * H, planned=planned)
+        torch.cuda.synchronize()
+        if planned:
+            assert gpu.last_kernel().startswith(PLAIN_KERNEL), gpu.last_kernel()
+        outs.append(gs)
+    assert bool((outs[0] >= 0).all())
+    for b in (0, cut - 1, cut, cut + 1, batch - 1):
+        one = torch.full((H, W), -1.0, dtype=torch.float32, device="cuda")
+        gpu.adjoint_device(rq, gd[b].data_ptr(), dW, one.data_ptr(), W, st, planned="any")
+        torch.cuda.synchronize()
+        assert torch.equal(outs[0][b], one) and torch.equal(outs[1][b], one), b
+
+
 # 6.  guard bands
 def test_rotated_adjoint_stays_inside_its_buffers(gpu, knife_golden):
     """gdst is the guarded SOURCE (NaN around it), gsrc the guarded destination (sentinel everywhere), the three layouts of

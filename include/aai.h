@@ -161,7 +161,17 @@ int aai_resample_f64(const aai_request *req, const double *src, int64_t src_stri
  * that one builds the plan (K1: weight tables uploaded with blocking copies; rotated requests: one-off scans of the
  * geometry for pixels that need the double-precision pass, read back with a blocking copy), so it synchronises with the
  * device and must not run inside a stream capture.  aai_prepare takes that cost up front; plans are cached per
- * process (32 most recently used), shared by batches, row bands (rotated requests) and streams. */
+ * process (32 most recently used), shared by batches, row bands (rotated requests) and streams.
+ *
+ * Stream order, with no host wait anywhere: every device entry of this header and of its extension headers (forward, batches,
+ * typed and interleaved sources, row bands, each shard of the multi-device entry on its own stream, the adjoint family) behaves
+ * like ONE kernel launched on `stream`.  Work enqueued on `stream` before the call -- the producer of d_src / d_gdst may still be
+ * running when the call returns -- is complete before the call reads or writes anything; work enqueued on `stream` after the call
+ * -- a consumer of d_dst / d_gsrc, or the next frame overwriting d_src -- starts only after everything the call enqueued has
+ * finished, the double-precision pass the library runs on a side stream of its own and the adjoint's stream-ordered scratch
+ * included.  That holds on the legacy default stream (NULL) exactly as on a stream the caller created, blocking or not, for
+ * several streams calling at once on one request, and for replays of a captured call.  Synchronising `stream` alone is enough to
+ * read the result on the host.  tests/test_gpu_stream_order.py is the check. */
 int aai_prepare(const aai_request *req, int32_t channels /* 1 for plain images; 2..4: interleaved */);
 /* What building a plan does on the device (inside aai_prepare, or inside the first resampling call of a request):
  *   - K1 (rotation by a multiple of 90 degrees): uploads the weight tables; checks the separable model against the

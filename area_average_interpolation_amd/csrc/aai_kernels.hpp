@@ -23,8 +23,7 @@ struct ImageView {
 // Small facts the launchers and their *_can_* predicates share, each stated once (host code; no kernel calls these).
 // bytes per element of a source type
 constexpr size_t src_elem_size(int srcType) { return srcType == SRC_U8 ? 1 : srcType == SRC_U16 ? 2 : 4; }
-// LDS words one window slot takes with `chan` interleaved channels of elemSize bytes each (8-bit RGB(A): one word, like a plain image)
-constexpr int slot_words(size_t elemSize, int chan) { return elemSize == 4 ? chan : (elemSize == 2 ? (chan + 1) / 2 : 1); }
+// (slot_words -- LDS words per window slot of interleaved channels -- lives in aai_rot_quad.hpp, where the CPU replay can ask it too)
 
 // ---- K1: axis-aligned separable kernel ----------------------------------------------------------------
 struct AxisLaunch {

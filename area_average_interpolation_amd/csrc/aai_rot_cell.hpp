@@ -51,6 +51,11 @@ namespace aai {
 // much as the loads (1:1 at 30 degrees 824 -> 934 us, config 5's replicated source 2.65 -> 3.04 ms).
 // (c, s = cos, sin of the reduced angle.)  The kernel's launcher and the CPU replay of its fetches (tests/emulation) both ask this function.
 AAI_HD int cell_wave_rows(double side, int scale, double c, double s) { return scale <= 1 && side >= 2.35 && (c < s ? c : s) >= 0.1 ? 2 : 1; }
+// Interleaved channels (aai_cell_multi_kernel, 64 x 1 wave): instantiated for windows up to 6 x 6 whose win * win * words KiB of LDS per block
+// (slot_words, aai_rot_quad.hpp) stay within 64; cell_can_serve leaves every other window to aai_quad_multi_kernel.  Asked by the
+// launcher, by cell_can_serve and by the variant probe of the test-suite, like cell_wave_rows.
+constexpr int kCellMultiMaxWin = 6, kCellMultiMaxKiB = 64;
+AAI_HD constexpr bool cell_multi_fits_lds(int win, int words) { return win <= kCellMultiMaxWin && win * win * words <= kCellMultiMaxKiB; }
 constexpr int cell_wave_lanes(int waveRows) { return 64 / waveRows; }              // cell columns a wave evaluates per cell row
 constexpr int cell_wave_cols(int waveRows) { return 64 / waveRows - 1; }           // dst columns it completes (the last cell column only feeds its left neighbour)
 

@@ -139,6 +139,20 @@ AAI_HD int quad_fast_parts(double side, double c, double s)
     return win <= kQuadMaxWin ? 1 : (win <= 2 * kQuadMaxWin ? 2 : (win <= 4 * kQuadMaxWin ? 4 : 0));
 }
 
+// ---- what the launchers key their choice of instantiation on, beside the window sizes of QuadConsts ---------------------------------
+// Like cell_wave_rows (aai_rot_cell.hpp), each is stated once: the launchers, their *_can_* predicates and the variant probe of the
+// test-suite (tests/emulation) all ask these functions.  Host code; no kernel calls them.
+// LDS words one window slot takes with `chan` interleaved channels of elemSize bytes each (8-bit RGB(A): one word, like a plain image)
+AAI_HD constexpr int slot_words(size_t elemSize, int chan) { return elemSize == 4 ? chan : (elemSize == 2 ? (chan + 1) / 2 : 1); }
+// aai_quad_multi_kernel stages win^2 slots of `words` LDS words per lane, i.e. win * win * words KiB per 256-lane block: two
+// workgroups must fit a CU's 160 KiB (quad_can_address keeps wider windows on the double-precision kernels)
+constexpr int kQuadMultiMaxKiB = 80;
+AAI_HD constexpr bool quad_multi_fits_lds(int win, int words) { return win * win * words <= kQuadMultiMaxKiB; }
+// Fast mode, one window: does the row-shaped wave (aai_quad_fast_rows_kernel) serve the geometry instead of the 16 x 4 wave?  With
+// replication, and without it while a dst pixel is at most 1.6 source pixels wide (measurements: aai_rotated_quad.hip, launch_quad_win;
+// images of 4 GiB and more keep the 16 x 4 wave whatever this says).
+AAI_HD bool quad_fast_row_shaped(double side, int scale) { return scale > 1 || side <= 1.6; }
+
 // the sum of the parts' partial sums, in the order the lanes of a dst pixel exchange them (a butterfly over lane distance 1, 2,
 // 4, ...): v[0] afterwards
 template <typename F>

@@ -79,7 +79,6 @@ constexpr int cell_min_waves(int win) { return win <= 4 ? 6 : (cell_waves_per_si
 __device__ __forceinline__ size_t flag_word(int dx, int dy, int tilesX) { return ((size_t)(dy >> 4) * tilesX + (dx >> 4)) * 4 + ((dy & 15) >> 2); }
 __device__ __forceinline__ int flag_bit(int dx, int dy) { return ((dy & 3) << 4) | (dx & 15); }
 
-constexpr int kCellMultiMaxKiB = 64;        // the interleaved kernel's window: WIN * WIN * WORDS KiB of LDS at most
 constexpr int kCellXcdRowsDefault = 2;      // row blocks per XCD band without replication (profiles/r04_fast_xcd.txt)
 constexpr int kCellWaves = kQuadBlock / 64;          // waves of a workgroup: consecutive row segments of ONE strip of 63 dst columns
 
@@ -501,7 +500,7 @@ template <typename T, int WIN, int WORDS>
 hipError_t launch_cell_multi_words(const RotLaunch &r, const QuadConsts<float> &q, const CellConsts<float> &z, const QuadMap &m, const T *src, ImageView sv,
                                    float *dst, ImageView dv, int batch, const unsigned long long *skipMasks, hipStream_t stream)
 {
-    if constexpr (WIN * WIN * WORDS > kCellMultiMaxKiB) return hipErrorInvalidValue;          // (cell_can_serve keeps such windows on the quad kernel)
+    if constexpr (!cell_multi_fits_lds(WIN, WORDS)) return hipErrorInvalidValue;          // (cell_can_serve keeps such windows on the quad kernel)
     else {
         const int rows = r.dyEnd - r.dyBase;
         const int rowsPerWave = cell_rows_per_wave(r.dW, rows, batch, r.side / (m.scale > 0 ? m.scale : 1));
@@ -625,7 +624,7 @@ bool cell_can_serve(const RotLaunch &r, int srcType, ImageView sv)
         // of packed words is unpacked for four dst pixels' sums, and four channels' sums cross lanes and rows)
         if (esz != 4 && r.scale <= 1 && !r.preferCell) return false;
         const CellConsts<float> z = make_cell_consts<float>(r.side, r.c, r.s);
-        if (z.win > 6 || z.win * z.win * slot_words((size_t)esz, r.chan) > kCellMultiMaxKiB) return false;
+        if (!cell_multi_fits_lds(z.win, slot_words((size_t)esz, r.chan))) return false;
         return !spans_4gib(r, srcType, sv);
     }
     if (!spans_4gib(r, srcType, sv)) return true;

@@ -298,7 +298,7 @@ hipError_t launch_quad_win(const RotLaunch &r, const QuadConsts<float> &q, const
         // ... and without replication while a dst pixel is at most 1.6 source pixels wide (1.5:1 at 17.5 degrees 237 -> 189 us, 1:1 at
         // 45 degrees 480 -> 426; from 2:1 on the slanted line of source pixels a row-shaped wave reads costs more than its stores
         // save: 2:1 at 45 degrees 148 -> 206 us, 3:1 at 17.5 degrees 100 -> 158) -- profiles/r03_store_paths.txt
-        const bool rowShaped = m.scale > 1 || r.side <= 1.6;
+        const bool rowShaped = quad_fast_row_shaped(r.side, m.scale);
         if (rowShaped && m.anchorRows == 0) {
             // (images of 4 GiB and more keep the 16 x 4 wave: their anchor rows are sized for it)
             const dim3 rows((r.dW + 63) / 64 + 1, grid.y, batch);
@@ -361,17 +361,17 @@ template <typename T, int WIN>
 hipError_t launch_quad_multi_win(const RotLaunch &r, const QuadConsts<float> &q, const QuadMap &m, const T *src, ImageView sv, float *dst, ImageView dv,
                                  int batch, const unsigned long long *skipMasks, hipStream_t stream)
 {
-    // quad_can_address() keeps WIN * WIN * words <= 80 KiB of LDS per block
+    // quad_can_address() keeps the window within quad_multi_fits_lds
     const int words = slot_words(sizeof(T), r.chan);
     if (sizeof(T) == 1) return launch_quad_multi_words<T, WIN, 1>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
     if (sizeof(T) == 2) {
         if (words == 1) return launch_quad_multi_words<T, WIN, 1>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
         return launch_quad_multi_words<T, WIN, (sizeof(T) == 2 ? 2 : 1)>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
     }
-    if (WIN * WIN * words > 80) return hipErrorInvalidValue;
-    if (words == 2) return launch_quad_multi_words<T, WIN, (sizeof(T) == 4 && WIN * WIN * 2 <= 80 ? 2 : 1)>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
-    if (words == 3) return launch_quad_multi_words<T, WIN, (sizeof(T) == 4 && WIN * WIN * 3 <= 80 ? 3 : 1)>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
-    return launch_quad_multi_words<T, WIN, (sizeof(T) == 4 && WIN * WIN * 4 <= 80 ? 4 : 1)>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
+    if (!quad_multi_fits_lds(WIN, words)) return hipErrorInvalidValue;
+    if (words == 2) return launch_quad_multi_words<T, WIN, (sizeof(T) == 4 && quad_multi_fits_lds(WIN, 2) ? 2 : 1)>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
+    if (words == 3) return launch_quad_multi_words<T, WIN, (sizeof(T) == 4 && quad_multi_fits_lds(WIN, 3) ? 3 : 1)>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
+    return launch_quad_multi_words<T, WIN, (sizeof(T) == 4 && quad_multi_fits_lds(WIN, 4) ? 4 : 1)>(r, q, m, src, sv, dst, dv, batch, skipMasks, stream);
 }
 
 // FAMILIES: which kernel families this translation unit holds (see "translation units" below): 1 = area mode, plain images;
@@ -458,7 +458,7 @@ bool quad_can_address(const RotLaunch &r, int srcType, ImageView sv)
     if (r.chan > 1) {
         // interleaved channels: the staged window (win^2 slots of `words` LDS words per lane) must leave room for two
         // workgroups per CU
-        if (win * win * slot_words(src_elem_size(srcType), r.chan) > 80) return false;
+        if (!quad_multi_fits_lds(win, slot_words(src_elem_size(srcType), r.chan))) return false;
     }
     return true;
 }

@@ -1396,4 +1396,62 @@ int aai_emu_strip_stats(const aai_request *rq, int *nStrips, int *maxOutputsPerS
     return AAI_OK;
 }
 
+// The variant probe (tests/rot_variants.py): everything the launchers of the rotated lattice key their choice of a template
+// instantiation on, for a request with `channels` interleaved channels of srcElemBytes bytes each, computed by the header functions
+// the launchers themselves call (make_quad_consts, make_cell_consts, make_cell_quad_consts, cell_wave_rows, quad_supported /
+// cell_supported / quad_wide_parts / quad_fast_parts through make_rot_launch, slot_words, quad_multi_fits_lds, cell_multi_fits_lds,
+// quad_fast_row_shaped).  out[0 .. ROTV_COUNT): see the enum.  ROTV_FAMILY restates the PRECEDENCE of rot_family (aai_rotated.hip)
+// and the small-output rule of cell_can_serve (aai_rotated_cell.hip) for images below 4 GiB -- the one thing here that is written
+// twice, and the GPU suite checks it against aai_last_kernel() in every case it runs.  Returns an AAI_* status; an axis-aligned or
+// sampler request reports ROTF_NONE.
+enum RotVariantFamily { ROTF_NONE = 0, ROTF_QUAD = 1, ROTF_QUAD_FAST = 2, ROTF_QUAD_MULTI = 3, ROTF_CELL = 4, ROTF_CELL_MULTI = 5, ROTF_WIDE = 6,
+                        ROTF_WIDE_FAST = 7, ROTF_FP64 = 8 };
+enum RotVariantField {
+    ROTV_FAMILY = 0,        // RotVariantFamily: the family that serves the request as it stands (policy bits and canvas included)
+    ROTV_SCALE,             // integer pre-expansion of the source (SCALED = scale > 1)
+    ROTV_QUAD, ROTV_CELL, ROTV_WIDE,            // RotLaunch::quad / cell / wide
+    ROTV_WIN, ROTV_WIN_FULL, ROTV_PARTS,        // the window of the request's mode (area: win / winFull / parts; fast: winFast / winFastFull / partsFast)
+    ROTV_HIPREC,            // QuadConsts::hiPrec as the quad and wide launchers see it
+    ROTV_CELL_WIN, ROTV_CELL_HIPREC, ROTV_CELL_WAVE_ROWS,       // the cell launcher's window, precision variant and wave shape
+    ROTV_WORDS,             // LDS words per window slot
+    ROTV_FAST_ROW_SHAPED,   // fast mode, one window: the row-shaped wave
+    ROTV_QUAD_MULTI_FITS, ROTV_CELL_MULTI_FITS,                 // the two LDS admission rules of interleaved windows
+    ROTV_DW, ROTV_DH,
+    ROTV_COUNT
+};
+int aai_emu_rot_variant(const aai_request *rq, int channels, int srcElemBytes, int *out)
+{
+    for (int i = 0; i < ROTV_COUNT; ++i) out[i] = 0;
+    Geometry g;
+    std::string msg;
+    const int rc = make_geometry(*rq, g, msg);
+    if (rc != AAI_OK) return rc;
+    out[ROTV_DW] = g.dW; out[ROTV_DH] = g.dH; out[ROTV_SCALE] = g.scale;
+    if (g.axisAligned || (rq->mode != AAI_MODE_AREA && rq->mode != AAI_MODE_FAST)) return AAI_OK;
+    RotLaunch r = make_rot_launch(g, rq->mode, rq->policy);
+    r.chan = channels;
+    const bool fast = rq->mode == AAI_MODE_FAST, multi = channels > 1;
+    const QuadConsts<float> q = make_quad_consts<float>(r.side, r.c, r.s, r.policy, r.scale);
+    const QuadConsts<float> qz = make_cell_quad_consts<float>(r.side, r.c, r.s, r.policy);
+    const CellConsts<float> z = make_cell_consts<float>(r.side, r.c, r.s);
+    const int words = slot_words((size_t)srcElemBytes, channels);
+    out[ROTV_QUAD] = r.quad; out[ROTV_CELL] = r.cell; out[ROTV_WIDE] = r.wide;
+    out[ROTV_WIN] = fast ? q.winFast : q.win; out[ROTV_WIN_FULL] = fast ? q.winFastFull : q.winFull; out[ROTV_PARTS] = fast ? q.partsFast : q.parts;
+    out[ROTV_HIPREC] = q.hiPrec;
+    out[ROTV_CELL_WIN] = z.win; out[ROTV_CELL_HIPREC] = qz.hiPrec; out[ROTV_CELL_WAVE_ROWS] = cell_wave_rows(r.side, r.scale, r.c, r.s);
+    out[ROTV_WORDS] = words;
+    out[ROTV_FAST_ROW_SHAPED] = quad_fast_row_shaped(r.side, r.scale) ? 1 : 0;
+    out[ROTV_QUAD_MULTI_FITS] = quad_multi_fits_lds(q.winFull, words) ? 1 : 0;
+    out[ROTV_CELL_MULTI_FITS] = cell_multi_fits_lds(z.win, words) ? 1 : 0;
+    // (rot_family's order: cell where cell_can_serve, then wide, then quad, then double precision)
+    bool cell = r.cell && !fast && (r.preferCell || (int64_t)((r.dW + 62) / 63) * ((r.dH + 7) / 8) >= 1024);
+    if (cell && multi) cell = !(srcElemBytes != 4 && r.scale <= 1 && !r.preferCell) && cell_multi_fits_lds(z.win, words);
+    int family = ROTF_FP64;
+    if (cell) family = multi ? ROTF_CELL_MULTI : ROTF_CELL;
+    else if (r.wide && !multi && r.scale == 1) family = fast ? ROTF_WIDE_FAST : ROTF_WIDE;
+    else if (r.quad && !(fast && multi) && (!multi || quad_multi_fits_lds(q.winFull, words))) family = multi ? ROTF_QUAD_MULTI : (fast ? ROTF_QUAD_FAST : ROTF_QUAD);
+    out[ROTV_FAMILY] = family;
+    return AAI_OK;
+}
+
 }  // extern "C"

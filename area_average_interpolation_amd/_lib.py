@@ -115,6 +115,12 @@ ROTATED_INTERLEAVED_ADJOINT_SYMBOLS = {
     "aai_adjoint_rotated_interleaved_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
 }
 
+# the extension header include/aai_adjoint_planned_interleaved.h
+PLANNED_INTERLEAVED_ADJOINT_SYMBOLS = {
+    "aai_adjoint_planned_interleaved_device_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_adjoint_planned_interleaved_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
+}
+
 _lib = None
 
 
@@ -136,7 +142,8 @@ def load():
                 pass
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()) + list(INTERLEAVED_ADJOINT_SYMBOLS.items()) +
-                                  list(ROTATED_ADJOINT_SYMBOLS.items()) + list(ROTATED_INTERLEAVED_ADJOINT_SYMBOLS.items())):
+                                  list(ROTATED_ADJOINT_SYMBOLS.items()) + list(ROTATED_INTERLEAVED_ADJOINT_SYMBOLS.items()) +
+                                  list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items())):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

@@ -277,26 +277,27 @@ def resample_device(request, src_ptr, src_stride, dst_ptr, dst_stride, stream=0,
         raise AaiError(rc, last_error())
 
 
-# (interleaved entry?, planned kind) -> (device entry, host entry).  There is no ("planned") row for the interleaved entries: no
-# interleaved transposed separable kernel exists to ask for.
+# (interleaved entry?, planned kind) -> (device entry, host entry).  The interleaved entries have no ("planned") row: the interleaved
+# transposed separable kernel is asked for with "separable" (aai_adjoint_planned_interleaved_*), which is planned at every geometry.
 _ADJOINT_ENTRY = {
     (False, "general"): ("aai_adjoint_batch_device_f32", "aai_adjoint_f32"),
     (False, "planned"): ("aai_adjoint_planned_batch_device_f32", "aai_adjoint_planned_f32"),
     (False, "any"): ("aai_adjoint_rotated_batch_device_f32", "aai_adjoint_rotated_f32"),
     (True, "general"): ("aai_adjoint_interleaved_device_f32", "aai_adjoint_interleaved_f32"),
     (True, "any"): ("aai_adjoint_rotated_interleaved_device_f32", "aai_adjoint_rotated_interleaved_f32"),
+    (True, "separable"): ("aai_adjoint_planned_interleaved_device_f32", "aai_adjoint_planned_interleaved_f32"),
 }
 
 
 def _planned_kind(planned, interleaved=False):
     """planned=False | True | "any" of the adjoint wrappers -> which family of entries serves the call.  The interleaved wrappers take
-    False or "any" only; True is refused there."""
+    False, "any" or "separable" only; True is refused there, and "separable" by the single-channel wrappers."""
     if interleaved:
         if planned is False:
             return "general"
-        if isinstance(planned, str) and planned == "any":
-            return "any"
-        raise ValueError('planned must be False or "any" for the interleaved adjoint, got %r' % (planned,))
+        if isinstance(planned, str) and planned in ("any", "separable"):
+            return planned
+        raise ValueError('planned must be False, "any" or "separable" for the interleaved adjoint, got %r' % (planned,))
     if isinstance(planned, str):
         if planned != "any":
             raise ValueError('planned must be False, True or "any", got %r' % (planned,))
@@ -384,14 +385,18 @@ def adjoint_interleaved_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr
     handle.  Channel c gets the bits adjoint_device gives plane c alone; a pair's weight is computed once for all channels.
     planned="any": aai_adjoint_rotated_interleaved_device_f32 -- the same bits; at a general rotation from the single-channel plan's cached
     sums and the plain closed forms (the first call of a geometry builds them and synchronises, see adjoint_rotated_prepare, which
-    serves every channel count), at multiples of 90 degrees the general interleaved kernels.  planned=True raises ValueError: there is
-    no interleaved transposed separable kernel."""
+    serves every channel count), at multiples of 90 degrees the general interleaved kernels.
+    planned="separable": aai_adjoint_planned_interleaved_device_f32 -- "any" at every general rotation, and at multiples of 90 degrees
+    the interleaved transposed separable kernel (aai_axis_adjoint_multi_kernel<C>, fp32) on the single-channel plan's adjoint tables:
+    channel c gets the bits adjoint_device(..., planned=True) gives plane c (adjoint_rotated_prepare builds the tables).
+    planned=True raises ValueError: the interleaved wrappers name the path they ask for."""
     _adjoint_device(True, planned, request, batch, channels, gdst_ptr, dst_stride, dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
 
 
 def adjoint_interleaved_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle,
                              mode=L.MODE_AREA, policy=L.POLICY_REFERENCE, planned=False):
-    """Host-buffer interleaved adjoint (aai_adjoint_interleaved_f32; planned="any": aai_adjoint_rotated_interleaved_f32): gdst is the [dH, dW, C] gradient with respect to the output of
+    """Host-buffer interleaved adjoint (aai_adjoint_interleaved_f32; planned="any": aai_adjoint_rotated_interleaved_f32;
+    planned="separable": aai_adjoint_planned_interleaved_f32): gdst is the [dH, dW, C] gradient with respect to the output of
     resample_interleaved_host(src of shape (H, W, C), ...), src_shape = (H, W) or (H, W, C); returns (code, message, gsrc [H, W, C]
     float32 or None)."""
     _planned_kind(planned, interleaved=True)                 # (a bad `planned` is reported before a bad gdst)

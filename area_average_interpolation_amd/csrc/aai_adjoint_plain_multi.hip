@@ -19,6 +19,12 @@
 //   aai_adjoint_gather_listed_multi_kernel<MODE, C>  one lane per listed source pixel: the general per-pair code
 //                                                    (adjoint_gather_multi), OVERWRITING the C floats of that pixel -- the
 //                                                    multi-channel twin of aai_adjoint_gather_listed_kernel
+//   aai_adjoint_norm_listed_multi_kernel<MODE, C>    one lane per listed DST pixel: the general normaliser (adjoint_normalised_multi)
+//                                                    into the C doubles of that pixel of n -- the multi-channel twin of
+//                                                    aai_adjoint_norm_listed_kernel.  Not part of the path above: with the listed
+//                                                    gather it is the correction pass behind the interleaved transposed separable
+//                                                    kernel (launch_adjoint_listed_multi; aai_axis_adjoint_multi.hip), which has no
+//                                                    sums to scale by and so normalises the listed dst pixels itself
 // n is fp64 with the channels innermost, [dH][dW][C], the layout of aai_adjoint_multi.hip.  The C floats of a pixel of gdst / gsrc are
 // accessed one by one: a row stride is any number of elements, so nothing wider than 4 bytes is aligned.
 // The group of C doubles of a pixel of n is read in the source as C plain 8-byte loads -- the form that shipped.  The scratch is the
@@ -74,6 +80,59 @@ __global__ __launch_bounds__(kListedMultiBlock) void aai_adjoint_gather_listed_m
     float *g = gsrc + (int64_t)blockIdx.z * sv.imageStride + (int64_t)sy * sv.rowStride + (int64_t)sx * C;
 #pragma unroll
     for (int c = 0; c < C; ++c) g[c] = (float)acc[c];
+}
+
+template <int MODE, int C>
+__global__ __launch_bounds__(kListedMultiBlock) void aai_adjoint_norm_listed_multi_kernel(RotLaunch r, const float *__restrict__ gdst, ImageView dv,
+                                                                                         double *__restrict__ n, const uint2 *__restrict__ list, unsigned count)
+{
+    const unsigned i = blockIdx.x * kListedMultiBlock + threadIdx.x;
+    if (i >= count) return;
+    const int dx = (int)list[i].x, dy = (int)list[i].y;
+    const float *g = gdst + (int64_t)blockIdx.z * dv.imageStride + (int64_t)dy * dv.rowStride + (int64_t)dx * C;
+    double gd[C], out[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) gd[c] = (double)g[c];
+    adjoint_normalised_multi<MODE, C>(r, dx, dy, gd, out);
+    double *nd = n + (((int64_t)blockIdx.z * r.dH + dy) * r.dW + dx) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) nd[c] = out[c];
+}
+
+template <int MODE, int C>
+static hipError_t launch_adjoint_listed_multi_as(const RotLaunch &r, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
+                                                 const uint2 *dstList, unsigned nDst, const uint2 *srcList, unsigned nSrc, hipStream_t stream)
+{
+    const dim3 block(kListedMultiBlock, 1, 1), gridD((nDst + kListedMultiBlock - 1) / kListedMultiBlock, 1, batch), gridS((nSrc + kListedMultiBlock - 1) / kListedMultiBlock, 1, batch);
+    hipLaunchKernelGGL((aai_adjoint_norm_listed_multi_kernel<MODE, C>), gridD, block, 0, stream, r, gdst, dv, n, dstList, nDst);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((aai_adjoint_gather_listed_multi_kernel<MODE, C>), gridS, block, 0, stream, r, n, gsrc, sv, srcList, nSrc);
+    return hipGetLastError();
+}
+
+template <int MODE>
+static hipError_t launch_adjoint_listed_multi_mode(const RotLaunch &r, int channels, int batch, const float *gdst, ImageView dv, double *n, float *gsrc,
+                                                   ImageView sv, const uint2 *dstList, unsigned nDst, const uint2 *srcList, unsigned nSrc, hipStream_t stream)
+{
+    switch (channels) {
+    case 2: return launch_adjoint_listed_multi_as<MODE, 2>(r, batch, gdst, dv, n, gsrc, sv, dstList, nDst, srcList, nSrc, stream);
+    case 3: return launch_adjoint_listed_multi_as<MODE, 3>(r, batch, gdst, dv, n, gsrc, sv, dstList, nDst, srcList, nSrc, stream);
+    case 4: return launch_adjoint_listed_multi_as<MODE, 4>(r, batch, gdst, dv, n, gsrc, sv, dstList, nDst, srcList, nSrc, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// The two passes of the general multi-channel adjoint over LISTS of pixels (the correction pass behind launch_axis_adjoint_multi): pass 1
+// over the nDst dst pixels of dstList into n (the other elements of n are neither written nor read), pass 2 over the nSrc source pixels
+// of srcList, whose C floats of gsrc it OVERWRITES.  `channels` in 2..4; n holds batch x dH x dW x channels doubles; `batch` <= 65535.
+hipError_t launch_adjoint_listed_multi(const RotLaunch &r, int channels, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
+                                       const uint2 *dstList, unsigned nDst, const uint2 *srcList, unsigned nSrc, hipStream_t stream)
+{
+    if (channels < 2 || channels > 4) return hipErrorInvalidValue;
+    if (batch <= 0 || !nDst || !nSrc) return hipSuccess;
+    return r.mode == AAI_MODE_FAST ? launch_adjoint_listed_multi_mode<AAI_MODE_FAST>(r, channels, batch, gdst, dv, n, gsrc, sv, dstList, nDst, srcList, nSrc, stream)
+                                   : launch_adjoint_listed_multi_mode<AAI_MODE_AREA>(r, channels, batch, gdst, dv, n, gsrc, sv, dstList, nDst, srcList, nSrc, stream);
 }
 
 template <int MODE, int C>

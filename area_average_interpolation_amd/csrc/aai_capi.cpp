@@ -22,6 +22,7 @@
 #include "../../include/aai_adjoint_interleaved.h"
 #include "../../include/aai_adjoint_rotated.h"
 #include "../../include/aai_adjoint_rotated_interleaved.h"
+#include "../../include/aai_adjoint_planned_interleaved.h"
 
 using namespace aai::engine;
 
@@ -94,7 +95,7 @@ int check_adjoint_request(const aai_request *rq, int batch, aai::Geometry &g)
     if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the adjoint.");
     return AAI_OK;
 }
-// ... and the images'.  The interleaved entries (aai_adjoint_interleaved_*, aai_adjoint_rotated_interleaved_*) check the channel count
+// ... and the images'.  The interleaved entries (aai_adjoint_interleaved_*, aai_adjoint_rotated_interleaved_*, aai_adjoint_planned_interleaved_*) check the channel count
 // right after the request, as the forward's interleaved entries report it, and the row length before the pointers; the single-channel
 // entries check neither.  Strides in elements of `channels` per pixel.
 int check_adjoint(const aai_request *rq, int batch, bool interleaved, int channels, const void *gdst, int64_t dstStride, const void *gsrc,
@@ -523,6 +524,19 @@ int aai_adjoint_rotated_interleaved_f32(const aai_request *req, int32_t channels
                                         aai_layout *layout)
 {
     return adjoint_host(ADJOINT_ROTATED, true, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
+}
+
+int aai_adjoint_planned_interleaved_device_f32(const aai_request *req, int32_t batch, int32_t channels,
+                                               const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                               float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    return adjoint_device(ADJOINT_SEPARABLE, true, req, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
+}
+
+int aai_adjoint_planned_interleaved_f32(const aai_request *req, int32_t channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride,
+                                        aai_layout *layout)
+{
+    return adjoint_host(ADJOINT_SEPARABLE, true, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
 int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)

@@ -769,12 +769,15 @@ int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry 
     const bool prepareOnly = dGdst == nullptr;
     // ---- the routing table (aai_engine.hpp): what the entry asked for -> the family whose launches serve the call
     const int kernel = pick_kernel(rq, g);
+    // (SEPARABLE is the one entry that asks for the interleaved transposed separable kernel; everywhere else it is ROTATED, line for line)
+    if (family == ADJOINT_SEPARABLE && (channels == 1 || kernel != AAI_KERNEL_AXIS)) family = ADJOINT_ROTATED;
     if (family == ADJOINT_ROTATED && kernel != AAI_KERNEL_ROTATED && kernel != AAI_KERNEL_FAST)      // reduced angle 0
         family = channels == 1 ? ADJOINT_PLANNED : ADJOINT_GENERAL;
     if (family == ADJOINT_PLANNED && (kernel != AAI_KERNEL_AXIS || channels != 1)) family = ADJOINT_GENERAL;
     PlanRef p;
-    if (family == ADJOINT_PLANNED) {
-        // the forward's plan under the forward's key (a packed fp32 image, one channel, the whole image)
+    if (family == ADJOINT_PLANNED || family == ADJOINT_SEPARABLE) {
+        // the forward's plan under the forward's key (a packed fp32 image, one channel, the whole image): its adjoint tables know pixels,
+        // not channels, and serve every channel count
         const int rc = acquire_plan(rq, g, -1, -1, 1, aai::ROT_FORM_QUAD, &p, /*onCallerStream*/ !prepareOnly, stream);
         if (rc != AAI_OK) return rc;
         std::lock_guard<std::mutex> lock(p->build);
@@ -799,17 +802,22 @@ int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry 
     const char *name = "";
     bool listed = false;                 // the plan has lists for a pass of the general kernels behind its own
     aai::AxisAdjointLaunch a{};
-    if (family == ADJOINT_PLANNED) {
-        const aai::AxisLaunch f = make_axis_launch(*p, 1, dstStride);
+    if (family == ADJOINT_PLANNED || family == ADJOINT_SEPARABLE) {
+        // (ka, kb) -> the first element of a dst PIXEL: the forward's mapping (make_axis_launch) with a pixel of `channels` elements.  Not
+        // make_axis_launch(*p, channels, ...): that divides the plan's nA by the channel count, and this plan's nA is in pixels already.
+        const aai::AxisTables &t = p->tabs;
+        const int64_t sa = t.transposed ? dstStride : channels, sb = t.transposed ? channels : dstStride;
         a.laneTab = p->dLane; a.rowTab = p->dRow; a.colRange = p->dColRange; a.rowRange = p->dRowRange;
         a.srcW = g.W; a.srcH = g.H;
-        a.outBase = f.outBase; a.outStrideA = f.outStrideA; a.outStrideB = f.outStrideB;
-        name = "aai_axis_adjoint_kernel";
+        a.outStrideA = t.flipA ? -sa : sa;
+        a.outStrideB = t.flipB ? -sb : sb;
+        a.outBase = (t.flipA ? (int64_t)(t.nA - 1) * sa : 0) + (t.flipB ? (int64_t)(t.nB - 1) * sb : 0);
+        name = "aai_axis_adjoint_kernel";            // (SEPARABLE: its launcher names the instantiation)
         listed = p->adjSrcCount != 0 && p->adjDstCount != 0;
-        if (!listed) imageBytes = 0;     // the transposed separable kernel needs no scratch, only the correction pass does
+        if (!listed) imageBytes = 0;     // the transposed separable kernels need no scratch, only the correction pass does
     } else if (family == ADJOINT_ROTATED) listed = p->adjSrcCount != 0;
     // (AAI_POLICY_DOUBLE_PRECISION / AAI_POLICY_PREFER_CELL choose between forward kernels; the adjoint has one, in double precision)
-    const aai::RotLaunch r = family != ADJOINT_PLANNED || listed ? aai::make_rot_launch(g, rq.mode, rq.policy) : aai::RotLaunch{};
+    const aai::RotLaunch r = (family != ADJOINT_PLANNED && family != ADJOINT_SEPARABLE) || listed ? aai::make_rot_launch(g, rq.mode, rq.policy) : aai::RotLaunch{};
     const uint2 *srcList = p ? static_cast<const uint2 *>(p->dAdjSrcList) : nullptr, *dstList = p ? static_cast<const uint2 *>(p->dAdjDstList) : nullptr;
     auto launch = [&](int nb, const float *gd, float *gs, double *n) -> hipError_t {
         hipError_t e = hipSuccess;
@@ -820,6 +828,11 @@ int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry 
         case ADJOINT_PLANNED:
             e = aai::launch_axis_adjoint(a, nb, gd, dv, gs, sv, stream, nullptr);
             if (e == hipSuccess && listed) e = aai::launch_adjoint_listed(r, nb, gd, dv, n, gs, sv, dstList, p->adjDstCount, srcList, p->adjSrcCount, stream);
+            return e;
+        case ADJOINT_SEPARABLE:
+            e = aai::launch_axis_adjoint_multi(a, channels, nb, gd, dv, gs, sv, stream, &name);
+            if (e == hipSuccess && listed)
+                e = aai::launch_adjoint_listed_multi(r, channels, nb, gd, dv, n, gs, sv, dstList, p->adjDstCount, srcList, p->adjSrcCount, stream);
             return e;
         case ADJOINT_ROTATED:
             if (channels != 1) return aai::launch_adjoint_plain_multi(r, channels, nb, gd, dv, p->dAdjSums, n, gs, sv, srcList, p->adjSrcCount, stream, &name);

@@ -175,9 +175,14 @@ inline int chunk_images(int batch, size_t imageBytes)
 //               (adjState 2)
 //               axis plan with its adjoint tables (adjState 1)      PLANNED
 //   ROTATED     reduced angle 0, one channel                        as PLANNED above
-//               reduced angle 0, 2..4 channels                      GENERAL (there is no interleaved transposed separable kernel)
+//               reduced angle 0, 2..4 channels                      GENERAL (the interleaved transposed separable kernel is SEPARABLE's)
 //               plan that keeps the general adjoint (rotAdjState 2) GENERAL
 //               plan with its sums (rotAdjState 1)                  ROTATED
+//   SEPARABLE   one channel, or not axis-aligned                    as ROTATED above, line for line
+//               axis-aligned, 2..4 channels: the single-channel     GENERAL
+//               plan is wide or dense, ... (adjState 2)
+//               the single-channel plan has its adjoint tables      SEPARABLE
+//               (adjState 1)
 //
 //   GENERAL  no plan, nothing blocks: pass 1 and the gather of aai_adjoint.hip (one channel) or aai_adjoint_multi.hip (2..4; a pair's
 //            weight computed once, channel c with the bits of plane c alone), fp64.
@@ -189,12 +194,17 @@ inline int chunk_images(int batch, size_t imageBytes)
 //            aai_adjoint_plain_multi.hip with `channels` accumulators) and, where the plan lists source pixels, the general gather over
 //            them: "<plain name>+listed".  The general adjoint's bits.
 //
+//   SEPARABLE  the forward's SINGLE-channel plan with the adjoint tables of PLANNED (the same tables: inverse ranges and lists know pixels,
+//            not channels), then aai_axis_adjoint_multi_kernel<C> (aai_axis_adjoint_multi.hip: one lane per row element, fp32, no scratch)
+//            and, where the plan has lists, the listed passes of the general multi-channel adjoint behind it
+//            (launch_adjoint_listed_multi): "aai_axis_adjoint_multi_kernel<C>+listed".  Channel c has PLANNED's bits of plane c.
+//
 // A plan's tables are built on first need, under its `build` lock: that blocks; afterwards a call only enqueues.  The launches of
-// PLANNED and ROTATED hold the plan's `launch` lock; GENERAL takes none.  Scratch: dW x dH x channels doubles per image in flight
-// (PLANNED: dW x dH where there are lists, else none), stream-ordered from the device pool's memory pool (hipMallocFromPoolAsync /
+// PLANNED, SEPARABLE and ROTATED hold the plan's `launch` lock; GENERAL takes none.  Scratch: dW x dH x channels doubles per image in flight
+// (PLANNED and SEPARABLE: only where there are lists, else none), stream-ordered from the device pool's memory pool (hipMallocFromPoolAsync /
 // hipFreeAsync on `stream`), the batch in chunks of chunk_images().
 // dGdst == NULL: prepare only -- build what the family needs and return (aai_adjoint_prepare, aai_adjoint_rotated_prepare).
-enum AdjointFamily { ADJOINT_GENERAL, ADJOINT_PLANNED, ADJOINT_ROTATED };
+enum AdjointFamily { ADJOINT_GENERAL, ADJOINT_PLANNED, ADJOINT_ROTATED, ADJOINT_SEPARABLE };
 int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
                     int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 

@@ -158,6 +158,16 @@ struct AxisAdjointLaunch {
 hipError_t launch_axis_adjoint(const AxisAdjointLaunch &a, int batch, const float *gdst, ImageView dv, float *gsrc, ImageView sv,
                                hipStream_t stream, const char **kernelName);
 
+// the same for `channels` = 2..4 interleaved channels (aai_axis_adjoint_multi.hip): one lane per ELEMENT of a source row.  a.srcW / a.srcH
+// in pixels and a.outBase / outStrideA / outStrideB the mapping of PIXELS onto elements of gdst (a dst pixel is `channels` elements wide);
+// the tables are the single-channel plan's.  Channel c gets the bits launch_axis_adjoint gives plane c.  `batch` <= 65535.
+hipError_t launch_axis_adjoint_multi(const AxisAdjointLaunch &a, int channels, int batch, const float *gdst, ImageView dv, float *gsrc, ImageView sv,
+                                     hipStream_t stream, const char **kernelName);
+// ... and its correction pass (aai_adjoint_plain_multi.hip): launch_adjoint_listed for `channels` = 2..4, the same lists (they know no
+// channels); n holds batch x dH x dW x channels doubles, channels innermost.  Channel c gets the bits launch_adjoint_listed gives plane c.
+hipError_t launch_adjoint_listed_multi(const RotLaunch &r, int channels, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
+                                       const uint2 *dstList, unsigned nDst, const uint2 *srcList, unsigned nSrc, hipStream_t stream);
+
 // ---- utilities -----------------------------------------------------------------------------------------
 hipError_t launch_synth(float *dst, int W, int H, int64_t stride, uint64_t seed, hipStream_t stream);
 hipError_t launch_synth_rows(float *dst, int W, int H, int row0, int row1, int64_t stride, uint64_t seed, hipStream_t stream);

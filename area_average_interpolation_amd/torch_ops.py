@@ -4,7 +4,8 @@
 ``torch.autograd.Function``: its backward is the library's adjoint (aai_adjoint_batch_device_f32), gsrc = W^T gdst with the
 forward's own weights -- not an approximation through ``grid_sample`` (``planned_backward=True``: the planned adjoint,
 aai_adjoint_planned_batch_device_f32; ``"any"``: aai_adjoint_rotated_batch_device_f32, planned at every rotation; ``"interleaved"``:
-``"any"`` plus aai_adjoint_rotated_interleaved_device_f32 for channels_last tensors at general rotations).  Both launch on ``torch.cuda.current_stream()`` of the
+``"any"`` plus aai_adjoint_rotated_interleaved_device_f32 for channels_last tensors at general rotations; ``"channels_last"``:
+``"interleaved"`` plus aai_adjoint_planned_interleaved_device_f32 for channels_last tensors at multiples of 90 degrees).  Both launch on ``torch.cuda.current_stream()`` of the
 tensor's device and only enqueue work.
 
 torch is imported here, not by the package: ``import area_average_interpolation_amd`` works without it.
@@ -34,10 +35,15 @@ def _ensure_prepared(rq, channels=1):
 #   rotated      "any" at a general rotation: the plan's sums and knife lists
 #   interleaved  the tables of aai_adjoint_rotated_interleaved_device_f32 live on the SINGLE-channel plan of the geometry, which the
 #                interleaved forward (prepared for C channels) does not build: aai_adjoint_rotated_prepare builds both
+#   separable    the tables of aai_adjoint_planned_interleaved_device_f32 at a multiple of 90 degrees are those of "planned", and they too
+#                live on the SINGLE-channel plan (plan_shape(rq, 1)), which the interleaved forward does not build: missing while that plan
+#                is missing or says adjoint=none; aai_adjoint_rotated_prepare builds the plan and the tables
 _ADJOINT_TABLES = {
     "planned": (lambda t: "kernel=%d" % L.KERNEL_AXIS in t and "dense=0" in t and "adjoint=none" in t, api.adjoint_prepare, "True"),
     "rotated": (lambda t: "rot_adjoint=none" in t, api.adjoint_rotated_prepare, '"any"'),
     "interleaved": (lambda t: not t or "rot_adjoint=none" in t, api.adjoint_rotated_prepare, '"interleaved"'),
+    "separable": (lambda t: not t or ("kernel=%d" % L.KERNEL_AXIS in t and "dense=0" in t and "adjoint=none" in t), api.adjoint_rotated_prepare,
+                  '"channels_last"'),
 }
 
 
@@ -46,7 +52,7 @@ def _ensure_adjoint_prepared(rq, route):
     aai_adjoint_rotated_prepare): do that in the forward, outside any stream capture.  Inside a capture missing tables are an error,
     not a hidden synchronisation."""
     missing, prepare, shown = _ADJOINT_TABLES[route]
-    if not missing(api.plan_shape(rq).split()):
+    if not missing(api.plan_shape(rq, 1).split()):
         return
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("resample(planned_backward=%s): this geometry has no adjoint tables on this device yet and the current "
@@ -56,10 +62,10 @@ def _ensure_adjoint_prepared(rq, route):
 
 
 def _normalise_planned(planned_backward):
-    """False | True | "any" | "interleaved" (anything else that is a string raises)"""
+    """False | True | "any" | "interleaved" | "channels_last" (anything else that is a string raises)"""
     if isinstance(planned_backward, str):
-        if planned_backward not in ("any", "interleaved"):
-            raise ValueError('planned_backward must be False, True, "any" or "interleaved", got %r' % (planned_backward,))
+        if planned_backward not in ("any", "interleaved", "channels_last"):
+            raise ValueError('planned_backward must be False, True, "any", "interleaved" or "channels_last", got %r' % (planned_backward,))
         return planned_backward
     return bool(planned_backward)
 
@@ -100,7 +106,8 @@ class _ResampleInterleaved(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, rq, lay, planned=False):
-        """planned: False (the general interleaved adjoint) or "any" (aai_adjoint_rotated_interleaved_device_f32)"""
+        """planned: False (the general interleaved adjoint), "any" (aai_adjoint_rotated_interleaved_device_f32) or "separable"
+        (aai_adjoint_planned_interleaved_device_f32 at a geometry the separable kernel serves)"""
         B, C, H, W = x.shape
         dH, dW = lay.dst_height, lay.dst_width
         y = torch.empty((B, C, dH, dW), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
@@ -108,7 +115,7 @@ class _ResampleInterleaved(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _ensure_prepared(rq, C)
             if planned and ctx.needs_input_grad[0]:
-                _ensure_adjoint_prepared(rq, "interleaved")
+                _ensure_adjoint_prepared(rq, "separable" if planned == "separable" else "interleaved")
             api.resample_interleaved_device(rq, C, x.data_ptr(), W * C, y.data_ptr(), dW * C, stream=torch.cuda.current_stream().cuda_stream,
                                             batch=B, src_image_stride=H * W * C, dst_image_stride=dH * dW * C)
         return y
@@ -145,6 +152,10 @@ def _resample_nchw(x, geometry, mode, policy, planned):
     if x.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
         raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
     interleaved = 2 <= C <= 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
+    if planned == "channels_last":
+        if interleaved and lay.kernel == L.KERNEL_AXIS:
+            return _ResampleInterleaved.apply(x, rq, lay, "separable"), iso      # zero-copy AND the transposed separable backward
+        planned = "interleaved"      # every other input: exactly "interleaved"
     if planned == "interleaved":
         if interleaved and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST):
             return _ResampleInterleaved.apply(x, rq, lay, "any"), iso       # zero-copy AND the planned backward
@@ -179,15 +190,19 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     every input but one: a (B, C, H, W) tensor dense in torch.channels_last with 2 <= C <= 4 at a geometry the rotated area / fast
     kernels serve keeps the zero-copy interleaved route AND gets a planned backward, aai_adjoint_rotated_interleaved_device_f32 (the
     same tables, on the single-channel plan, built by the forward when x requires grad; the same rule inside a stream capture).  Any
+    "channels_last" -- exactly "interleaved" for every input but one: such a channels_last tensor at a geometry the SEPARABLE kernel
+    serves (aai_query: AAI_KERNEL_AXIS, rotations by multiples of 90 degrees) keeps the zero-copy interleaved route too, and its backward
+    is aai_adjoint_planned_interleaved_device_f32, the interleaved transposed separable kernel (the tables of True, on the single-channel
+    plan, built by the forward through aai_adjoint_rotated_prepare when x requires grad; the same rule inside a stream capture).  Any
     other string raises ValueError.
 
     (B, C, H, W) input takes one of two routes, every plane resampled with the same geometry.  Which one, by planned_backward
     (cl = dense in channels_last with 2 <= C <= 4; "other" = bilinear / bicubic):
-      geometry served by      False              True               "any"              "interleaved"
-      separable kernel, cl    interleaved        planar             planar             planar
-      rotated / fast, cl      interleaved        interleaved        planar             interleaved, planned backward
-      other, cl               interleaved        interleaved        interleaved        interleaved
-      any, not cl             planar             planar             planar             planar
+      geometry served by      False              True               "any"              "interleaved"                   "channels_last"
+      separable kernel, cl    interleaved        planar             planar             planar                          interleaved, separable backward
+      rotated / fast, cl      interleaved        interleaved        planar             interleaved, planned backward   interleaved, planned backward
+      other, cl               interleaved        interleaved        interleaved        interleaved                     interleaved
+      any, not cl             planar             planar             planar             planar                          planar
       planar       x.contiguous() viewed as (B * C, H, W) through the 3-D operator and reshaped back: the 3-D operator's bits plane by
                    plane, planned_backward honoured.  Every input the interleaved route does not take, channels_last tensors with
                    C = 1 or C > 4 among them.
@@ -204,7 +219,17 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
                    kernels serve the route stays interleaved and the backward is aai_adjoint_rotated_interleaved_device_f32 on a
                    channels_last gy -- y and x.grad are channels_last and have the bits of this route's default (y: the interleaved
                    forward's; x.grad: per channel the default single-channel adjoint's, which are also the "any" planar route's).
-                   At the separable kernel's geometries it stays planar: the transposed separable kernel is single-channel.
+                   At the separable kernel's geometries "interleaved" stays planar.
+                   planned_backward="channels_last" lifts the first half as well: at a geometry the separable kernel serves the route
+                   stays interleaved and the backward is aai_adjoint_planned_interleaved_device_f32 on a channels_last gy
+                   (aai_axis_adjoint_multi_kernel<C>, one lane per row element) -- y and x.grad are channels_last; y has the
+                   interleaved forward's bits (within the library's tolerance of the planar forward), x.grad[b, c] the bits of the
+                   planar planned_backward=True gradient.  A wide separable plan (AAI_KERNEL_AXIS_WIDE) is "other" in every column.
+                   The rule for an exception was: a row class whose backward is not faster on this route than on the planar one
+                   keeps the planar route.  Measured on an MI355X for C = 3 and 4 (profiles/adjoint_axis_interleaved_time.txt, one
+                   run; DESIGN.md section 9 quotes it), the backward alone with the planar route's permutes included: this route's
+                   median is below the planar route's in all 16 rows -- 1.5-2.0x when down-sampling, 2.8-4.5x at x2 up-sampling at 270
+                   degrees (1.080 -> 0.384 ms for C = 3 in area mode) -- so there is no exception.
                    Measured on an MI355X for C = 3 and 4 (profiles/adjoint_rotated_interleaved_time.txt, one run; DESIGN.md section 9
                    quotes it): the new backward is 1.9-4.2x faster than the general interleaved backward and 2.5-3.5x faster than C
                    planned single-channel backwards on planes split beforehand (the planar route's permutes not counted), with
@@ -228,7 +253,7 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     if xb.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
         raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
     planned = _normalise_planned(planned_backward)
-    if planned == "interleaved":
+    if planned in ("interleaved", "channels_last"):
         planned = "any"              # there are no channels to interleave
     y = _Resample.apply(xb, rq, lay, planned)
     return (y if x.dim() == 3 else y.squeeze(0)), (lay.dst_iso_x, lay.dst_iso_y)

@@ -33,7 +33,9 @@ extern "C" {
  *   - channels == 1: the code behind aai_adjoint_rotated_batch_device_f32 (aai_adjoint_rotated.h), its kernels and bits.
  *   - Reduced angle 0 (rotations by multiples of 90 degrees), channels 2..4: forwarded to the code behind
  *     aai_adjoint_interleaved_device_f32, the GENERAL interleaved adjoint, with its bits (aai_last_kernel() names
- *     aai_adjoint_gather_multi_kernel).  An interleaved transposed separable kernel does not exist and is out of scope.  NOTE that the
+ *     aai_adjoint_gather_multi_kernel).  The interleaved transposed separable kernel (aai_axis_adjoint_multi_kernel<C>) is NOT reached
+ *     through these entries, whose routing and bits are pinned: aai_adjoint_planned_interleaved_device_f32
+ *     (aai_adjoint_planned_interleaved.h) is the entry that asks for it, and is this entry everywhere else.  NOTE that the
  *     single-channel entry differs there: it forwards to the fp32 transposed separable kernel (aai_axis_adjoint_kernel).
  *   - Every other rotation, area or fast mode, channels 2..4: the plan aai_adjoint_rotated_batch_device_f32 uses -- the forward's
  *     SINGLE-channel plan, same key -- with the tables aai_adjoint_rotated.h describes: S (8 bytes per dst pixel) and the list of

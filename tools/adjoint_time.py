@@ -23,7 +23,16 @@ aai_adjoint_interleaved_device_f32, the general interleaved adjoint, (c) C calls
 beforehand (the split is not timed) -- with the ratios of the medians (b)/(a) and (c)/(a), whether (a)'s 90th percentile lies below
 (b)'s 10th, and whether (a) and (b) have the same bits at the end of each row.  (profiles/adjoint_rotated_interleaved_time.txt)
 
-usage: python tools/adjoint_time.py [--planned | --channels | --rotated | --rotated --channels] [--launches N] [--out FILE]      (the table also goes to stdout)"""
+--planned --channels: the interleaved planned adjoint at multiples of 90 degrees (aai_adjoint_planned_interleaved_device_f32, after
+aai_adjoint_rotated_prepare) on PLANNED_GEOMETRIES, both modes, C = 3 and C = 4, the legs taking turns in one process -- (a)
+aai_adjoint_interleaved_device_f32, the general interleaved adjoint, (b) C calls of aai_adjoint_planned_batch_device_f32 on planes split
+beforehand (the split is not timed), (c) the new entry, and (d) the torch operator's BACKWARD alone on a (1, C, H, W) channels_last input
+with a channels_last gy: the planar route (planned_backward=True, its permutes included) against planned_backward="channels_last" --
+with (a)/(c), (c)/(b), whether (c)'s 90th percentile lies below (a)'s 10th, whether (c) and (b) have the same bits, and the two torch
+medians at the end of each row; the header lines state the three conditions and the rows that miss them.
+(profiles/adjoint_axis_interleaved_time.txt)
+
+usage: python tools/adjoint_time.py [--planned | --channels | --rotated | --rotated --channels | --planned --channels] [--launches N] [--out FILE]      (the table also goes to stdout)"""
 import argparse
 import os
 import subprocess
@@ -103,6 +112,130 @@ def child_rotated_channels(name, mode, channels, launches):
               np.median(t["general"]) / np.median(t["new"]), np.median(t["planar"]) / np.median(t["new"]), "yes" if clear else "NO",
               "same" if same else "DIFFERENT", "same" if same_planar else "DIFFERENT", kernels["new"], kernels["planar"],
               " ".join(tok for tok in aai.plan_shape(rq).split() if tok.split("=")[0] in ("rot_adjoint", "knife"))), flush=True)
+
+
+def child_planned_channels(name, mode, channels, launches):
+    import numpy as np
+    import torch
+    import area_average_interpolation_amd as aai
+    from area_average_interpolation_amd import torch_ops
+    aai.set_device(0)
+    _, W, H, sr, dr, ang = [g for g in PLANNED_GEOMETRIES if g[0] == name][0]
+    C = channels
+    iso = ((W - 1) / 2, (H - 1) / 2)
+    rq = aai.make_request(W, H, sr, dr, iso, ang, mode=mode)
+    lay = aai.query(rq)[2]
+    dW, dH = lay.dst_width, lay.dst_height
+    st = torch.cuda.current_stream().cuda_stream
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    gd = torch.rand((dH, dW, C), dtype=torch.float32, device="cuda", generator=gen)
+    planes = gd.permute(2, 0, 1).contiguous()                       # split beforehand: not part of any leg
+    new = torch.empty((H, W, C), dtype=torch.float32, device="cuda")
+    general = torch.empty_like(new)
+    ps = torch.empty((C, H, W), dtype=torch.float32, device="cuda")
+    aai.adjoint_rotated_prepare(rq)                                 # the single-channel plan and its axis tables: every channel count
+    kernels = {}
+
+    def run_general():
+        aai.adjoint_interleaved_device(rq, C, gd.data_ptr(), dW * C, general.data_ptr(), W * C, st)
+        kernels["general"] = aai.last_kernel()
+
+    def run_planar():
+        for c in range(C):
+            aai.adjoint_device(rq, planes[c].data_ptr(), dW, ps[c].data_ptr(), W, st, planned=True)
+        kernels["planar"] = aai.last_kernel()
+
+    def run_new():
+        aai.adjoint_interleaved_device(rq, C, gd.data_ptr(), dW * C, new.data_ptr(), W * C, st, planned="separable")
+        kernels["new"] = aai.last_kernel()
+
+    # (d) the torch operator's backward alone: one forward per route, its graph kept
+    x = torch.rand((1, C, H, W), dtype=torch.float32, device="cuda", generator=gen).contiguous(memory_format=torch.channels_last)
+    gy = gd.unsqueeze(0).permute(0, 3, 1, 2)                        # (1, C, dH, dW), dense in channels_last
+    routes = {}
+    for key, planned in (("torch planar", True), ("torch cl", "channels_last")):
+        xr = x.clone(memory_format=torch.preserve_format).requires_grad_(True)
+        y, _ = torch_ops.resample(xr, sr, dr, iso, ang, mode=mode, planned_backward=planned)
+        routes[key] = (xr, y)
+
+    def backward(key):
+        xr, y = routes[key]
+        xr.grad = None
+        y.backward(gy, retain_graph=True)
+
+    runs = {"general": run_general, "planar": run_planar, "new": run_new,
+            "torch planar": lambda: backward("torch planar"), "torch cl": lambda: backward("torch cl")}
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in runs}
+    for _ in range(launches):
+        for key, fn in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[key].append(a.elapsed_time(b))
+    same_planar = torch.equal(new.permute(2, 0, 1).contiguous().view(torch.int32), ps.view(torch.int32))
+    gp, gc = routes["torch planar"][0].grad, routes["torch cl"][0].grad
+    same_torch = torch.equal(gp.contiguous().view(torch.int32), gc.contiguous().view(torch.int32)) and gc.is_contiguous(memory_format=torch.channels_last)
+    gdd = general.double()
+    dev = float(((new.double() - gdd).abs() / gdd.abs().clamp_min(1e-3 * float(gdd.abs().max()))).max())
+    t = {k: np.array(v) for k, v in times.items()}
+    cell = lambda v: "%8.3f ms (%.3f..%.3f)" % (np.median(v), np.percentile(v, 10), np.percentile(v, 90))
+    clear = np.percentile(t["new"], 90) < np.percentile(t["general"], 10)
+    row = "%s %s C=%d" % (name, "area" if mode == aai.MODE_AREA else "fast", C)
+    print("%-10s %-4s C=%d %5dx%-5d -> %5dx%-5d  (a) general interleaved %s  (b) %d planned single-channel calls %s  (c) new entry %s  "
+          "(a)/(c) %6.1f  (c)/(b) %5.2f  p90(c) < p10(a) %s  bits (c)=(b) %s  deviation from (a) %.2e  (d) torch backward: planar route %s  "
+          "channels_last route %s  planar/channels_last %5.2f  grads %s  [%s; %s]" % (
+              name, "area" if mode == aai.MODE_AREA else "fast", C, W, H, dW, dH, cell(t["general"]), C, cell(t["planar"]), cell(t["new"]),
+              np.median(t["general"]) / np.median(t["new"]), np.median(t["new"]) / np.median(t["planar"]), "yes" if clear else "NO",
+              "same" if same_planar else "DIFFERENT", dev, cell(t["torch planar"]), cell(t["torch cl"]),
+              np.median(t["torch planar"]) / np.median(t["torch cl"]), "same" if same_torch else "DIFFERENT", kernels["new"],
+              " ".join(tok for tok in aai.plan_shape(rq).split() if tok.split("=")[0] in ("flagged", "dense", "adjoint"))), flush=True)
+    # for the parent's header lines: row | (c) clear of (a) | (c)/(b) | torch channels_last median below planar's | the two torch medians
+    print("@ %s | %d | %.3f | %d | %.3f %.3f" % (row, clear, np.median(t["new"]) / np.median(t["planar"]),
+                                               np.median(t["torch cl"]) < np.median(t["torch planar"]), np.median(t["torch planar"]), np.median(t["torch cl"])), flush=True)
+
+
+def planned_channels_table(launches, out):
+    """the parent of child_planned_channels: the rows, then the header lines that state the three conditions with the rows that miss them"""
+    rows, facts = [], []
+    for g in PLANNED_GEOMETRIES:
+        for mode in (1, 2):
+            for channels in (3, 4):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--planned", "--channels", "--launches", str(launches),
+                                    "--child", g[0], str(mode), str(channels)], capture_output=True, text=True, timeout=240)
+                if r.returncode != 0:
+                    sys.stderr.write(r.stdout + r.stderr)
+                    return r.returncode or 1
+                line = [ln for ln in r.stdout.splitlines() if ln.startswith(g[0])][-1]
+                print(line, flush=True)
+                rows.append(line)
+                f = [x.strip() for x in [ln for ln in r.stdout.splitlines() if ln.startswith("@ ")][-1][2:].split("|")]
+                facts.append((f[0], int(f[1]), float(f[2]), int(f[3]), f[4]))
+    unclear = [f[0] for f in facts if not f[1]]
+    slower = ["%s (%.2f)" % (f[0], f[2]) for f in facts if f[2] > 1.0]
+    torch_slower = ["%s (planar, channels_last medians in ms: %s)" % (f[0], f[4]) for f in facts if not f[3]]
+    ratios = [f[2] for f in facts]
+    head = ["# median (10th..90th percentile) of %d launches each, device events, the legs taking turns, one process per row: (a) "
+            "aai_adjoint_interleaved_device_f32, (b) C calls of aai_adjoint_planned_batch_device_f32 on pre-split planes, (c) "
+            "aai_adjoint_planned_interleaved_device_f32, (d) the torch backward alone, planar route (planned_backward=True, permutes included) "
+            "and planned_backward=\"channels_last\"" % launches,
+            "# condition 1, (c) against (a): (c)'s 90th percentile below (a)'s 10th in every row -- %s" % (
+                "holds in all %d rows" % len(facts) if not unclear else "MISSED in: " + "; ".join(unclear)),
+            "# condition 2, (c) against (b): (c)/(b) between %.2f and %.2f over the rows -- %s" % (
+                min(ratios), max(ratios), "(c) is slower than (b) in no row" if not slower else "(c) is SLOWER than (b) in: " + "; ".join(slower)),
+            "# condition 3, (d): the channels_last route's median below the planar route's -- %s" % (
+                "holds in all %d rows: no row class keeps the planar route" % len(facts) if not torch_slower else "MISSED in: " + "; ".join(torch_slower))]
+    for ln in head:
+        print(ln, flush=True)
+    if out:
+        with open(out, "w") as f:
+            f.write("\n".join(head + rows) + "\n")
+    return 0
 
 
 def child_channels(name, mode, channels, launches):
@@ -306,10 +439,15 @@ def main():
     if args.launches < 20:
         ap.error("at least 20 timed launches")
     both = args.rotated and args.channels                      # the interleaved planned adjoint's table
-    if args.planned + args.channels + args.rotated > 1 and not (both and not args.planned):
-        ap.error("--planned, --channels and --rotated are separate tables (--rotated --channels is a fourth)")
+    axis_channels = args.planned and args.channels and not args.rotated      # ... and its table at multiples of 90 degrees
+    if args.planned + args.channels + args.rotated > 1 and not (both and not args.planned) and not axis_channels:
+        ap.error("--planned, --channels and --rotated are separate tables (--rotated --channels is a fourth, --planned --channels a fifth)")
+    if axis_channels and not args.child:
+        return planned_channels_table(args.launches, args.out)
     if args.child:
-        if both:
+        if axis_channels:
+            child_planned_channels(args.child[0], int(args.child[1]), int(args.child[2]), args.launches)
+        elif both:
             child_rotated_channels(args.child[0], int(args.child[1]), int(args.child[2]), args.launches)
         elif args.channels:
             child_channels(args.child[0], int(args.child[1]), int(args.child[2]), args.launches)

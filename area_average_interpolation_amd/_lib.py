@@ -121,6 +121,15 @@ PLANNED_INTERLEAVED_ADJOINT_SYMBOLS = {
     "aai_adjoint_planned_interleaved_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
 }
 
+# the extension header include/aai_adjoint_sample.h: the adjoint of the bilinear / bicubic samplers (the argument lists of
+# aai_adjoint_batch_device_f32, aai_adjoint_f32, aai_adjoint_interleaved_device_f32, aai_adjoint_interleaved_f32)
+SAMPLE_ADJOINT_SYMBOLS = {
+    "aai_adjoint_sample_batch_device_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_adjoint_sample_f32": (ctypes.c_int, [_RQ, _P, _I64, _P, _I64, _LY]),
+    "aai_adjoint_sample_interleaved_device_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_adjoint_sample_interleaved_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
+}
+
 _lib = None
 
 
@@ -143,7 +152,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()) + list(INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(ROTATED_ADJOINT_SYMBOLS.items()) + list(ROTATED_INTERLEAVED_ADJOINT_SYMBOLS.items()) +
-                                  list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items())):
+                                  list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items()) + list(SAMPLE_ADJOINT_SYMBOLS.items())):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

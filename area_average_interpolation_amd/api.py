@@ -286,6 +286,9 @@ _ADJOINT_ENTRY = {
     (True, "general"): ("aai_adjoint_interleaved_device_f32", "aai_adjoint_interleaved_f32"),
     (True, "any"): ("aai_adjoint_rotated_interleaved_device_f32", "aai_adjoint_rotated_interleaved_f32"),
     (True, "separable"): ("aai_adjoint_planned_interleaved_device_f32", "aai_adjoint_planned_interleaved_f32"),
+    # the samplers' adjoint (include/aai_adjoint_sample.h): reached by the adjoint_sample_* wrappers only, never through planned=
+    (False, "sample"): ("aai_adjoint_sample_batch_device_f32", "aai_adjoint_sample_f32"),
+    (True, "sample"): ("aai_adjoint_sample_interleaved_device_f32", "aai_adjoint_sample_interleaved_f32"),
 }
 
 
@@ -309,16 +312,18 @@ def _planned_interleaved_kind(planned):
     return _planned_kind(planned, interleaved=True)
 
 
-def _adjoint_device(interleaved, planned, request, batch, channels, gdst_ptr, dst_stride, dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream):
-    """the device entry of _ADJOINT_ENTRY; the interleaved entries take the channel count after the batch"""
-    fn = getattr(L.load(), _ADJOINT_ENTRY[interleaved, _planned_kind(planned, interleaved)][0])
+def _adjoint_device(interleaved, planned, request, batch, channels, gdst_ptr, dst_stride, dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream,
+                    kind=None):
+    """the device entry of _ADJOINT_ENTRY (kind: the family, where the caller names it instead of `planned`); the interleaved entries take
+    the channel count after the batch"""
+    fn = getattr(L.load(), _ADJOINT_ENTRY[interleaved, kind or _planned_kind(planned, interleaved)][0])
     rc = fn(_ref(request), 1 if batch is None else int(batch), *((int(channels),) if interleaved else ()), gdst_ptr, dst_stride,
             dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
     if rc != L.OK:
         raise AaiError(rc, last_error())
 
 
-def _adjoint_host(interleaved, planned, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy):
+def _adjoint_host(interleaved, planned, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, kind=None):
     """the host entry of _ADJOINT_ENTRY on gdst = [dH, dW] (single-channel) or [dH, dW, C] (interleaved)"""
     lib = L.load()
     H, W = int(src_shape[0]), int(src_shape[1])
@@ -332,7 +337,7 @@ def _adjoint_host(interleaved, planned, gdst, src_shape, src_resolution, dst_res
     if (g.shape[:2] if interleaved else g.shape) != (lay.dst_height, lay.dst_width):
         raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width) + tail,))
     gsrc = np.empty((H, W) + tail, dtype=np.float32)
-    fn = getattr(lib, _ADJOINT_ENTRY[interleaved, _planned_kind(planned, interleaved)][1])
+    fn = getattr(lib, _ADJOINT_ENTRY[interleaved, kind or _planned_kind(planned, interleaved)][1])
     rc = fn(_ref(rq), *((C,) if interleaved else ()), g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
     if rc != L.OK:
         return rc, last_error(), None
@@ -406,6 +411,44 @@ def adjoint_interleaved_host(gdst, src_shape, src_resolution, dst_resolution, sr
     if len(src_shape) == 3 and int(src_shape[2]) != g.shape[2]:
         raise ValueError("gdst has %d channels, src_shape %d" % (g.shape[2], int(src_shape[2])))
     return _adjoint_host(True, planned, g, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+
+
+def adjoint_sample_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None, dst_image_stride=0, src_image_stride=0):
+    """aai_adjoint_sample_batch_device_f32: gsrc = W(request)^T gdst on device-resident fp32 images for the BILINEAR and BICUBIC modes --
+    the transpose of what resample_device computes there (clamp-to-edge taps that add up, zero rows outside the extent, Keys a = -0.5).
+    Raw device pointers (ints), strides in elements, a hipStream_t handle; every element of the src_width x src_height gradient image
+    is written.  One deterministic gather per source pixel with double-precision weights; no plan, no scratch: the call only enqueues
+    and can be captured.  Area and fast requests raise AaiError (their adjoint is adjoint_device)."""
+    _adjoint_device(False, False, request, batch, 1, gdst_ptr, dst_stride, dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream, kind="sample")
+
+
+def adjoint_sample_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_BILINEAR, policy=L.POLICY_REFERENCE):
+    """Host-buffer adjoint of the samplers (aai_adjoint_sample_f32): gdst is the [dH, dW] gradient with respect to the output of
+    resample_host(src of shape src_shape = (H, W), ..., mode=MODE_BILINEAR or MODE_BICUBIC); returns (code, message, gsrc [H, W] float32
+    or None).  The device entry's bits."""
+    return _adjoint_host(False, False, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, kind="sample")
+
+
+def adjoint_sample_interleaved_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None, dst_image_stride=0,
+                                      src_image_stride=0):
+    """aai_adjoint_sample_interleaved_device_f32: adjoint_sample_device for images with `channels` (1..4) interleaved channels, element
+    (x, y, c) of image b at b * image_stride + y * stride + x * channels + c.  Channel c gets the bits adjoint_sample_device gives plane c
+    alone; a candidate's weight is computed once for all channels."""
+    _adjoint_device(True, False, request, batch, channels, gdst_ptr, dst_stride, dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream,
+                    kind="sample")
+
+
+def adjoint_sample_interleaved_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_BILINEAR,
+                                    policy=L.POLICY_REFERENCE):
+    """Host-buffer interleaved adjoint of the samplers (aai_adjoint_sample_interleaved_f32): gdst is the [dH, dW, C] gradient with respect to
+    the output of resample_interleaved_host(src of shape (H, W, C), ...), src_shape = (H, W) or (H, W, C); returns (code, message, gsrc
+    [H, W, C] float32 or None)."""
+    g = np.ascontiguousarray(gdst, dtype=np.float32)
+    if g.ndim != 3:
+        raise ValueError("gdst must be a [dH, dW, C] array")
+    if len(src_shape) == 3 and int(src_shape[2]) != g.shape[2]:
+        raise ValueError("gdst has %d channels, src_shape %d" % (g.shape[2], int(src_shape[2])))
+    return _adjoint_host(True, False, g, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, kind="sample")
 
 
 def resample_multi_device(request, shards, src_stride, src_image_stride, dst_stride, dst_image_stride):

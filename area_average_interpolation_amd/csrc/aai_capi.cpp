@@ -23,6 +23,7 @@
 #include "../../include/aai_adjoint_rotated.h"
 #include "../../include/aai_adjoint_rotated_interleaved.h"
 #include "../../include/aai_adjoint_planned_interleaved.h"
+#include "../../include/aai_adjoint_sample.h"
 
 using namespace aai::engine;
 
@@ -95,17 +96,28 @@ int check_adjoint_request(const aai_request *rq, int batch, aai::Geometry &g)
     if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the adjoint.");
     return AAI_OK;
 }
+// Its sibling for the samplers' adjoint (include/aai_adjoint_sample.h): ONLY the bilinear and bicubic modes.  The policy's rule and bits are
+// validated (check_request, as aai_query validates them) and otherwise ignored, as the forward's samplers ignore them.
+int check_adjoint_sample_request(const aai_request *rq, int batch, aai::Geometry &g)
+{
+    AAI_TRY(check_request(rq));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(request_geometry(*rq, g));
+    if (rq->mode == AAI_MODE_AREA) return fail(AAI_ERR_BAD_ARGUMENT, "The adjoint of AAI_MODE_AREA is aai_adjoint_batch_device_f32: the bilinear and bicubic modes only.");
+    if (rq->mode == AAI_MODE_FAST) return fail(AAI_ERR_BAD_ARGUMENT, "The adjoint of AAI_MODE_FAST is aai_adjoint_batch_device_f32: the bilinear and bicubic modes only.");
+    return AAI_OK;
+}
 // ... and the images'.  The interleaved entries (aai_adjoint_interleaved_*, aai_adjoint_rotated_interleaved_*, aai_adjoint_planned_interleaved_*) check the channel count
 // right after the request, as the forward's interleaved entries report it, and the row length before the pointers; the single-channel
 // entries check neither.  Strides in elements of `channels` per pixel.
-int check_adjoint(const aai_request *rq, int batch, bool interleaved, int channels, const void *gdst, int64_t dstStride, const void *gsrc,
-                  int64_t srcStride, aai::Geometry &g)
+int check_adjoint(AdjointFamily family, const aai_request *rq, int batch, bool interleaved, int channels, const void *gdst, int64_t dstStride,
+                  const void *gsrc, int64_t srcStride, aai::Geometry &g)
 {
     if (interleaved) {
         AAI_TRY(check_request(rq));
         AAI_TRY(check_channels(channels));
     }
-    AAI_TRY(check_adjoint_request(rq, batch, g));
+    AAI_TRY(family == ADJOINT_SAMPLE ? check_adjoint_sample_request(rq, batch, g) : check_adjoint_request(rq, batch, g));
     if (interleaved) AAI_TRY(check_row_length(g, channels));
     AAI_TRY(check_pointers(gdst, gsrc));
     return check_strides(g, channels, srcStride, dstStride);
@@ -116,7 +128,7 @@ int adjoint_device(AdjointFamily family, bool interleaved, const aai_request *re
                    int64_t dst_stride, int64_t dst_image_stride, float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(req, batch, interleaved, channels, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    AAI_TRY(check_adjoint(family, req, batch, interleaved, channels, d_gdst, dst_stride, d_gsrc, src_stride, g));
     if (batch == 0) { g_lastError.clear(); return AAI_OK; }
     AAI_TRY(require_device());
     AAI_TRY(enqueue_adjoint(family, *req, g, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
@@ -278,7 +290,7 @@ int adjoint_host(AdjointFamily family, bool interleaved, const aai_request *req,
                  int64_t src_stride, aai_layout *layout)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(req, 1, interleaved, channels, gdst, dst_stride, gsrc, src_stride, g));
+    AAI_TRY(check_adjoint(family, req, 1, interleaved, channels, gdst, dst_stride, gsrc, src_stride, g));
     AAI_TRY(require_device());
     const int64_t rowDst = (int64_t)g.dW * channels, rowSrc = (int64_t)g.W * channels;
     DeviceBuffer dGdst, dGsrc;
@@ -537,6 +549,31 @@ int aai_adjoint_planned_interleaved_f32(const aai_request *req, int32_t channels
                                         aai_layout *layout)
 {
     return adjoint_host(ADJOINT_SEPARABLE, true, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
+}
+
+int aai_adjoint_sample_batch_device_f32(const aai_request *req, int32_t batch,
+                                        const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                        float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    return adjoint_device(ADJOINT_SAMPLE, false, req, batch, 1, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
+}
+
+int aai_adjoint_sample_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
+{
+    return adjoint_host(ADJOINT_SAMPLE, false, req, 1, gdst, dst_stride, gsrc, src_stride, layout);
+}
+
+int aai_adjoint_sample_interleaved_device_f32(const aai_request *req, int32_t batch, int32_t channels,
+                                              const float *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                              float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    return adjoint_device(ADJOINT_SAMPLE, true, req, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, stream);
+}
+
+int aai_adjoint_sample_interleaved_f32(const aai_request *req, int32_t channels, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride,
+                                       aai_layout *layout)
+{
+    return adjoint_host(ADJOINT_SAMPLE, true, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
 }
 
 int aai_synth_rows_device_f32(float *d_dst, int32_t width, int32_t height, int32_t row0, int32_t row1, int64_t stride, uint64_t seed, void *stream)

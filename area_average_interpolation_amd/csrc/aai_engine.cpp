@@ -769,6 +769,7 @@ int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry 
     const bool prepareOnly = dGdst == nullptr;
     // ---- the routing table (aai_engine.hpp): what the entry asked for -> the family whose launches serve the call
     const int kernel = pick_kernel(rq, g);
+    // (SAMPLE -- the samplers' adjoint -- is never rerouted: none of the tests below names it)
     // (SEPARABLE is the one entry that asks for the interleaved transposed separable kernel; everywhere else it is ROTATED, line for line)
     if (family == ADJOINT_SEPARABLE && (channels == 1 || kernel != AAI_KERNEL_AXIS)) family = ADJOINT_ROTATED;
     if (family == ADJOINT_ROTATED && kernel != AAI_KERNEL_ROTATED && kernel != AAI_KERNEL_FAST)      // reduced angle 0
@@ -794,7 +795,7 @@ int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry 
     // ---- the launches.  A plan's launches are serialised between caller threads; the general family has no plan.
     int device = 0;
     std::unique_lock<std::mutex> lock;
-    if (family == ADJOINT_GENERAL) AAI_HIP(hipGetDevice(&device));
+    if (family == ADJOINT_GENERAL || family == ADJOINT_SAMPLE) AAI_HIP(hipGetDevice(&device));
     else { device = p->device; lock = std::unique_lock<std::mutex>(p->launch); }
     const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
     // scratch: one fp64 image of the dst size times the channels per image in flight
@@ -816,6 +817,7 @@ int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry 
         listed = p->adjSrcCount != 0 && p->adjDstCount != 0;
         if (!listed) imageBytes = 0;     // the transposed separable kernels need no scratch, only the correction pass does
     } else if (family == ADJOINT_ROTATED) listed = p->adjSrcCount != 0;
+    else if (family == ADJOINT_SAMPLE) imageBytes = 0;      // one gather, no scratch
     // (AAI_POLICY_DOUBLE_PRECISION / AAI_POLICY_PREFER_CELL choose between forward kernels; the adjoint has one, in double precision)
     const aai::RotLaunch r = (family != ADJOINT_PLANNED && family != ADJOINT_SEPARABLE) || listed ? aai::make_rot_launch(g, rq.mode, rq.policy) : aai::RotLaunch{};
     const uint2 *srcList = p ? static_cast<const uint2 *>(p->dAdjSrcList) : nullptr, *dstList = p ? static_cast<const uint2 *>(p->dAdjDstList) : nullptr;
@@ -834,6 +836,9 @@ int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry 
             if (e == hipSuccess && listed)
                 e = aai::launch_adjoint_listed_multi(r, channels, nb, gd, dv, n, gs, sv, dstList, p->adjDstCount, srcList, p->adjSrcCount, stream);
             return e;
+        case ADJOINT_SAMPLE:
+            return channels == 1 ? aai::launch_adjoint_sample(r, nb, gd, dv, gs, sv, stream, &name)
+                                 : aai::launch_adjoint_sample_multi(r, channels, nb, gd, dv, gs, sv, stream, &name);
         case ADJOINT_ROTATED:
             if (channels != 1) return aai::launch_adjoint_plain_multi(r, channels, nb, gd, dv, p->dAdjSums, n, gs, sv, srcList, p->adjSrcCount, stream, &name);
             e = aai::launch_adjoint_plain(r, nb, gd, dv, p->dAdjSums, n, gs, sv, stream, &name);

@@ -199,12 +199,16 @@ inline int chunk_images(int batch, size_t imageBytes)
 //            and, where the plan has lists, the listed passes of the general multi-channel adjoint behind it
 //            (launch_adjoint_listed_multi): "aai_axis_adjoint_multi_kernel<C>+listed".  Channel c has PLANNED's bits of plane c.
 //
+//   SAMPLE   (ADJOINT_SAMPLE: the entries of include/aai_adjoint_sample.h, bilinear / bicubic requests only -- the one family that takes
+//            them, and it takes no other mode.)  No plan, no scratch, nothing blocks: aai_adjoint_sample_kernel (aai_adjoint_sample.hip), one
+//            gather per source pixel in double precision, `channels` accumulators.  Never rerouted.
+//
 // A plan's tables are built on first need, under its `build` lock: that blocks; afterwards a call only enqueues.  The launches of
 // PLANNED, SEPARABLE and ROTATED hold the plan's `launch` lock; GENERAL takes none.  Scratch: dW x dH x channels doubles per image in flight
 // (PLANNED and SEPARABLE: only where there are lists, else none), stream-ordered from the device pool's memory pool (hipMallocFromPoolAsync /
 // hipFreeAsync on `stream`), the batch in chunks of chunk_images().
 // dGdst == NULL: prepare only -- build what the family needs and return (aai_adjoint_prepare, aai_adjoint_rotated_prepare).
-enum AdjointFamily { ADJOINT_GENERAL, ADJOINT_PLANNED, ADJOINT_ROTATED, ADJOINT_SEPARABLE };
+enum AdjointFamily { ADJOINT_GENERAL, ADJOINT_PLANNED, ADJOINT_ROTATED, ADJOINT_SEPARABLE, ADJOINT_SAMPLE };
 int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
                     int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 

@@ -168,6 +168,15 @@ hipError_t launch_axis_adjoint_multi(const AxisAdjointLaunch &a, int channels, i
 hipError_t launch_adjoint_listed_multi(const RotLaunch &r, int channels, int batch, const float *gdst, ImageView dv, double *n, float *gsrc, ImageView sv,
                                        const uint2 *dstList, unsigned nDst, const uint2 *srcList, unsigned nSrc, hipStream_t stream);
 
+// ---- the adjoint of the bilinear / bicubic samplers (aai_adjoint_sample.hip; body in aai_adjoint_sample_math.hpp): gsrc = W^T gdst, one
+// deterministic gather per source pixel in double precision, every element of gsrc written.  No scratch.  `batch` <= 65535.  Only enqueue.
+hipError_t launch_adjoint_sample(const RotLaunch &r, int batch, const float *gdst, ImageView dv, float *gsrc, ImageView sv, hipStream_t stream,
+                                 const char **kernelName);
+// the same for `channels` interleaved channels (element (x, y, c) at y * rowStride + x * channels + c): a candidate's weight is computed
+// once, channel c gets the bits launch_adjoint_sample gives plane c
+hipError_t launch_adjoint_sample_multi(const RotLaunch &r, int channels, int batch, const float *gdst, ImageView dv, float *gsrc, ImageView sv,
+                                       hipStream_t stream, const char **kernelName);
+
 // ---- utilities -----------------------------------------------------------------------------------------
 hipError_t launch_synth(float *dst, int W, int H, int64_t stride, uint64_t seed, hipStream_t stream);
 hipError_t launch_synth_rows(float *dst, int W, int H, int row0, int row1, int64_t stride, uint64_t seed, hipStream_t stream);

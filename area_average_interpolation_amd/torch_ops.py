@@ -6,7 +6,8 @@ forward's own weights -- not an approximation through ``grid_sample`` (``planned
 aai_adjoint_planned_batch_device_f32; ``"any"``: aai_adjoint_rotated_batch_device_f32, planned at every rotation; ``"interleaved"``:
 ``"any"`` plus aai_adjoint_rotated_interleaved_device_f32 for channels_last tensors at general rotations; ``"channels_last"``:
 ``"interleaved"`` plus aai_adjoint_planned_interleaved_device_f32 for channels_last tensors at multiples of 90 degrees).  Both launch on ``torch.cuda.current_stream()`` of the
-tensor's device and only enqueue work.
+tensor's device and only enqueue work.  ``sampler_backward=True`` makes the bilinear / bicubic modes differentiable as well: their backward
+is aai_adjoint_sample_batch_device_f32 (aai_adjoint_sample_interleaved_device_f32 for channels_last tensors).
 
 torch is imported here, not by the package: ``import area_average_interpolation_amd`` works without it.
 """
@@ -70,6 +71,10 @@ def _normalise_planned(planned_backward):
     return bool(planned_backward)
 
 
+# ctx.planned of a bilinear / bicubic request whose backward is the samplers' adjoint (sampler_backward=True): no plan, no tables
+_SAMPLER = "sampler"
+
+
 class _Resample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rq, lay, planned):
@@ -79,7 +84,7 @@ class _Resample(torch.autograd.Function):
         if B:
             with torch.cuda.device(x.device):
                 _ensure_prepared(rq)
-                if planned and ctx.needs_input_grad[0]:
+                if planned and planned != _SAMPLER and ctx.needs_input_grad[0]:
                     _ensure_adjoint_prepared(rq, "rotated" if planned == "any" and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST) else "planned")
                 api.resample_device(rq, x.data_ptr(), W, y.data_ptr(), lay.dst_width, stream=torch.cuda.current_stream().cuda_stream,
                                     batch=B, src_image_stride=H * W, dst_image_stride=lay.dst_height * lay.dst_width)
@@ -96,8 +101,12 @@ class _Resample(torch.autograd.Function):
         if B:
             dH, dW = gy.shape[1], gy.shape[2]
             with torch.cuda.device(gy.device):
-                api.adjoint_device(ctx.rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
-                                   batch=B, dst_image_stride=dH * dW, src_image_stride=H * W, planned=ctx.planned)
+                if ctx.planned == _SAMPLER:
+                    api.adjoint_sample_device(ctx.rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
+                                              batch=B, dst_image_stride=dH * dW, src_image_stride=H * W)
+                else:
+                    api.adjoint_device(ctx.rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
+                                       batch=B, dst_image_stride=dH * dW, src_image_stride=H * W, planned=ctx.planned)
         return gx, None, None, None
 
 
@@ -107,14 +116,15 @@ class _ResampleInterleaved(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rq, lay, planned=False):
         """planned: False (the general interleaved adjoint), "any" (aai_adjoint_rotated_interleaved_device_f32) or "separable"
-        (aai_adjoint_planned_interleaved_device_f32 at a geometry the separable kernel serves)"""
+        (aai_adjoint_planned_interleaved_device_f32 at a geometry the separable kernel serves); _SAMPLER: a bilinear / bicubic request,
+        aai_adjoint_sample_interleaved_device_f32"""
         B, C, H, W = x.shape
         dH, dW = lay.dst_height, lay.dst_width
         y = torch.empty((B, C, dH, dW), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         ctx.rq, ctx.src_shape, ctx.planned = rq, (B, C, H, W), planned
         with torch.cuda.device(x.device):
             _ensure_prepared(rq, C)
-            if planned and ctx.needs_input_grad[0]:
+            if planned and planned != _SAMPLER and ctx.needs_input_grad[0]:
                 _ensure_adjoint_prepared(rq, "separable" if planned == "separable" else "interleaved")
             api.resample_interleaved_device(rq, C, x.data_ptr(), W * C, y.data_ptr(), dW * C, stream=torch.cuda.current_stream().cuda_stream,
                                             batch=B, src_image_stride=H * W * C, dst_image_stride=dH * dW * C)
@@ -130,9 +140,17 @@ class _ResampleInterleaved(torch.autograd.Function):
         gx = torch.empty((B, C, H, W), dtype=torch.float32, device=gy.device, memory_format=torch.channels_last)
         dH, dW = gy.shape[2], gy.shape[3]
         with torch.cuda.device(gy.device):
-            api.adjoint_interleaved_device(ctx.rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, stream=torch.cuda.current_stream().cuda_stream,
-                                           batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C, planned=ctx.planned)
+            if ctx.planned == _SAMPLER:
+                api.adjoint_sample_interleaved_device(ctx.rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, stream=torch.cuda.current_stream().cuda_stream,
+                                                      batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C)
+            else:
+                api.adjoint_interleaved_device(ctx.rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, stream=torch.cuda.current_stream().cuda_stream,
+                                               batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C, planned=ctx.planned)
         return gx, None, None, None
+
+
+_NO_SAMPLER_ADJOINT = ("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad() "
+                       "(or pass sampler_backward=True for the samplers' own adjoint)")
 
 
 def _query(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy):
@@ -143,15 +161,21 @@ def _query(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, 
     return rq, lay
 
 
-def _resample_nchw(x, geometry, mode, policy, planned):
+def _resample_nchw(x, geometry, mode, policy, planned, sampler_backward=False):
     B, C, H, W = x.shape
     rq, lay = _query(W, H, *geometry, mode, policy)
     iso = (lay.dst_iso_x, lay.dst_iso_y)
     if B == 0 or C == 0:
         return torch.empty((B, C, lay.dst_height, lay.dst_width), dtype=torch.float32, device=x.device), iso
-    if x.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
-        raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
+    if x.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST) and not sampler_backward:
+        raise ValueError(_NO_SAMPLER_ADJOINT)
     interleaved = 2 <= C <= 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
+    if mode not in (L.MODE_AREA, L.MODE_FAST) and sampler_backward:
+        # the samplers' adjoint: the route is the forward's (planned_backward chooses between adjoints of the area / fast modes only)
+        if interleaved:
+            return _ResampleInterleaved.apply(x, rq, lay, _SAMPLER), iso
+        y = _Resample.apply(x.contiguous().view(B * C, H, W), rq, lay, _SAMPLER)
+        return y.view(B, C, lay.dst_height, lay.dst_width), iso
     if planned == "channels_last":
         if interleaved and lay.kernel == L.KERNEL_AXIS:
             return _ResampleInterleaved.apply(x, rq, lay, "separable"), iso      # zero-copy AND the transposed separable backward
@@ -171,10 +195,11 @@ def _resample_nchw(x, geometry, mode, policy, planned):
 
 
 def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
-             planned_backward=False):
+             *positional, sampler_backward=False, planned_backward=False):
     """Resample a CUDA/HIP fp32 tensor of shape (H, W), (B, H, W) or (B, C, H, W); returns ``(y, dst_isocenter)`` with y of shape
     (dH, dW), (B, dH, dW) or (B, C, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
-    bilinear / bicubic comparison paths have no adjoint: an x that requires grad raises ValueError there).  Non-contiguous
+    bilinear / bicubic comparison paths are differentiable only with sampler_backward=True, below: without it an x that requires grad
+    raises ValueError there).  Non-contiguous
     input is made contiguous; other dtypes raise TypeError, CPU tensors and other ranks ValueError, an invalid geometry
     AaiError.
 
@@ -234,7 +259,23 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
                    quotes it): the new backward is 1.9-4.2x faster than the general interleaved backward and 2.5-3.5x faster than C
                    planned single-channel backwards on planes split beforehand (the planar route's permutes not counted), with
                    identical bits in every row.
+    sampler_backward: False (the default) -- nothing changes: a bilinear / bicubic x that requires grad raises ValueError.  True -- such an
+    x is accepted and the operator is differentiable ONCE there too: the backward is aai_adjoint_sample_batch_device_f32 on
+    torch.cuda.current_stream(), gsrc = W^T gdst for the sampler's own W (the forward's affine map and quadrant pre-rotation,
+    clamp-to-edge taps that add up, exact zeros outside the image extent, Keys a = -0.5) -- one deterministic gather per source
+    pixel with double-precision weights, no plan, no scratch, nothing to prepare, capturable.  (B, C, H, W) input dense in
+    channels_last with 2 <= C <= 4 keeps the zero-copy interleaved route and its backward is
+    aai_adjoint_sample_interleaved_device_f32 (x.grad is channels_last, channel c with the bits of the single-channel entry on
+    plane c); every other input takes the planar route.  planned_backward is not consulted there, and in the area / fast modes
+    sampler_backward has no effect.
+
     B == 0 or C == 0 returns an empty tensor of the output's shape without a launch."""
+    # planned_backward keeps its place as the eighth positional argument (*positional holds at most that one); sampler_backward is
+    # keyword-only
+    if positional:
+        if len(positional) > 1 or planned_backward is not False:
+            raise TypeError("resample() takes at most 8 positional arguments, planned_backward the last of them, and planned_backward only once")
+        planned_backward = positional[0]
     if not isinstance(x, torch.Tensor):
         raise TypeError("resample() takes a torch.Tensor")
     if x.dtype != torch.float32:
@@ -244,16 +285,19 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     if not x.is_cuda:
         raise ValueError("resample() takes a tensor on a GPU (the library has no CPU path)")
     if x.dim() == 4:
-        return _resample_nchw(x, (src_resolution, dst_resolution, src_isocenter, rotation_angle), mode, policy, _normalise_planned(planned_backward))
+        return _resample_nchw(x, (src_resolution, dst_resolution, src_isocenter, rotation_angle), mode, policy, _normalise_planned(planned_backward),
+                              bool(sampler_backward))
     xb = (x if x.dim() == 3 else x.unsqueeze(0)).contiguous()
     rq = api.make_request(xb.shape[2], xb.shape[1], src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     rc, msg, lay = api.query(rq)
     if rc != L.OK:
         raise api.AaiError(rc, msg)
-    if xb.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST):
-        raise ValueError("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad()")
+    if xb.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST) and not sampler_backward:
+        raise ValueError(_NO_SAMPLER_ADJOINT)
     planned = _normalise_planned(planned_backward)
     if planned in ("interleaved", "channels_last"):
         planned = "any"              # there are no channels to interleave
+    if sampler_backward and mode not in (L.MODE_AREA, L.MODE_FAST):
+        planned = _SAMPLER           # (planned_backward chooses between adjoints of the area / fast modes only)
     y = _Resample.apply(xb, rq, lay, planned)
     return (y if x.dim() == 3 else y.squeeze(0)), (lay.dst_iso_x, lay.dst_iso_y)

@@ -27,7 +27,7 @@ namespace aai {
 
 namespace {
 
-constexpr int kWaves = 4;
+constexpr int kWaves = kAxisWaves;      // (aai_plan.hpp: the launch shape counts in them)
 constexpr int VEC = 4;         // source columns per lane and load: STRIP_COLS = 64 * VEC
 
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // dword-aligned 16-byte access
@@ -242,6 +242,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
         return CH ? (int64_t)(ka / a.outChan) * a.outStrideA + ka % a.outChan : (int64_t)ka * a.outStrideA;
     };
 
+    // (the five conditions of this chain are restated in axis_strip_branch, aai_plan.hpp, for the tests' variant probe: change both together)
     if (!CH && nOut <= 64 && (a.outStrideB == 1 || a.outStrideB == -1)) {
         // Quadrants 1 and 3 (pre-rotation by 90 / 270 degrees): the lane axis runs along dst y, so the output
         // rows of this workgroup are CONSECUTIVE DST COLUMNS of each lane's dst row.  Keep eight of them in
@@ -406,13 +407,16 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
 // whatever the grid order, because every store instruction writes into 64 different lines.  Here a wave gathers
 // kTileCols consecutive output rows (= dst columns) of its strip in an LDS tile and then stores the tile with lanes
 // running along dst x: 64 contiguous bytes per dst row and store.
-constexpr int kTileCols = 16;
+constexpr int kTileCols = kAxisTileCols;
 constexpr int kTilePitch = kTileCols + 1;              // odd pitch: the transposed reads hit 64 different banks
 constexpr int kTileWaveFloats = 64 * VEC + 8 + 256 * kTilePitch;
 
 // The output rows (columns of the tile) of one wave in a software pipeline kDepth deep: with 72 KiB of LDS per workgroup a SIMD
 // holds two waves, and a wave that waits for each output row's source rows before it asks for the next spends its life in load
 // latency (1:1 at 270 degrees: 2.6 TB/s so, 3.3 with the pipeline).  NR = source rows a window may have; taller ones: the plain path.
+// (The launch rules choose this kernel, and NR by axis_tile_window_rows, so that no window is taller than NR: tests/test_axis_variants_host.py
+// checks over the whole grid of tests/axis_variants.py -- ratios 0.25..12, all quadrants, both modes and isocenters on and off the lattice --
+// and over the suite's large cases that no launch has a `tall` window.  The plain path below is a safety net no request reaches.)
 template <bool NT, typename T, int NR, int kDepth, typename Finish>
 __device__ __forceinline__ void tile_columns(const T *__restrict__ img, int64_t rowStride, int colc, const AxisEntry *__restrict__ rowTab, int kb0, int nCols,
                                              Finish &&finish_column)
@@ -503,7 +507,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_tile_kernel(AxisLaunch a
     };
     // windows of at most four source rows (ratios up to 3): eight output rows in flight; up to eight rows (ratios up to 4, where a
     // strip still holds more than 64 outputs): four; anything taller takes the plain path
-    if (a.maxRowSpan <= 4) tile_columns<NT, T, 4, 8>(img, sv.rowStride, colc, rowTab, kb0, nCols, finish_column);
+    if (axis_tile_window_rows(a.maxRowSpan) == 4) tile_columns<NT, T, 4, 8>(img, sv.rowStride, colc, rowTab, kb0, nCols, finish_column);
     else tile_columns<NT, T, 8, 4>(img, sv.rowStride, colc, rowTab, kb0, nCols, finish_column);
     __syncthreads();
     // lane = dst x within the workgroup's 64 output rows (kb), read from the tile of the wave that computed it; wave w stores
@@ -559,8 +563,14 @@ template <typename T>
 static hipError_t launch_axis_typed(const AxisLaunch &a, const T *src, ImageView sv, float *dst, ImageView dv,
                                     int batch, hipStream_t stream, const char **kernelName)
 {
-    if (a.nA <= 0 || a.nB <= 0 || batch <= 0) return hipSuccess;
-    if (a.wide) {
+    // the launch shape -- which kernel, nontemporal loads, output rows per workgroup, the grid -- is axis_launch_shape's (aai_plan.hpp),
+    // where the measurements behind it are quoted
+    const AxisShapeFacts facts{a.nA, a.nB, a.nStrips, a.wide, a.maxRowSpan, a.rowsShared, a.maxOutputsPerStrip, a.transposed, a.tapStep,
+                               a.outStrideB, a.tuneRows, a.tuneNt, (int)sizeof(T), batch};
+    const AxisShape shape = axis_launch_shape(facts);
+    if (shape.kernel == AXIS_RUN_NOTHING) return hipSuccess;
+    const int nt = shape.nt, rows = shape.rows;
+    if (shape.kernel == AXIS_RUN_WIDE) {
         if (kernelName) *kernelName = "aai_axis_wide_kernel";
         for (int kb0 = 0; kb0 < a.nB; kb0 += 65535 * 4) {          // grid.y carries at most 65535 blocks of 4 rows
             dim3 grid((a.nA + 63) / 64, (std::min(a.nB - kb0, 65535 * 4) + 3) / 4, batch);
@@ -568,52 +578,14 @@ static hipError_t launch_axis_typed(const AxisLaunch &a, const T *src, ImageView
         }
         return hipGetLastError();
     }
-    // Launch shape (see the kernel comment for the measurements behind the defaults).
-    // Defaults from the sweeps in profiles/r01_axis_tune_*.txt (8192^2 sources):
-    //   * windows that share source rows between output rows (grid not pixel-aligned) want cached loads and
-    //     two rows per workgroup (5.8 vs 5.2 TB/s at 4:1); disjoint windows want nontemporal loads;
-    //   * >= 4 source rows per output row: one output row per workgroup (6.8 TB/s at 4:1; 5.3 at 8 rows);
-    //   * 2-3 source rows: four (5.0-5.2 TB/s vs 3.7-4.6 at one or two);
-    //   * ratios below 2 (129..256 outputs per strip, write-heavy): 32 rows per workgroup (4.2 TB/s at 1:1
-    //     vs 2.5 at four and 1.4 at one); the up-sampling path (more than 256 outputs per strip) prefers 4;
-    //   * 8- and 16-bit sources move 4x / 2x fewer bytes and are bound by per-wave latency, not by HBM: eight / four
-    //     rows per workgroup (8192^2 u8 -> 2048^2: 28 us at one row, 21 at eight; profiles/r01_typed_sources.txt).
-    int nt = a.rowsShared ? 0 : 1;
-    int rows = a.maxRowSpan >= 4 ? (a.rowsShared ? 2 : 1) : 4;
-    if (sizeof(T) < 4) {
-        // ... as long as that leaves a few workgroups per CU
-        const int want = sizeof(T) == 1 ? 8 : 4;
-        const int64_t stripBlocks = (int64_t)((a.nStrips + kWaves - 1) / kWaves) * batch;
-        while (rows < want && stripBlocks * ((a.nB + 2 * rows - 1) / (2 * rows)) >= 2048) rows *= 2;
-    }
-    if (a.transposed) {
-        // transposed quadrants: 2, 4 or 8 dst columns per lane and store; about 16 source rows per workgroup is the
-        // sweet spot between DRAM page locality and store width (8192^2 at 90 degrees: 4:1 5.9 TB/s at 4 rows vs 5.2 at
-        // 8; 8:1 6.0 at 2 vs 4.8 at 8; profiles/r01_axis_transposed.txt)
-        rows = a.maxRowSpan >= 8 ? 2 : (a.maxRowSpan >= 3 ? 4 : 8);
-        if (a.maxOutputsPerStrip > 64) rows = a.maxRowSpan >= 2 ? 4 : 16;     // the four-column path (ratios below 4)
-    }
-    if (!a.transposed && a.maxOutputsPerStrip > 128 && a.maxOutputsPerStrip <= 256) rows = 32;      // ratios below 2: write-heavy
-    // the plan's measured choice for this (geometry, device) -- fp32 sources only (aai_engine.cpp: tune_axis_plan)
-    if (sizeof(T) == 4 && a.tuneRows > 0) { rows = a.tuneRows; nt = a.tuneNt; }
-    // (measured, profiles/r01_axis_transposed.txt: wins below 2:1 -- 1:1 1.8 -> 2.3 TB/s, x4 up-sampling 1.2 -> 1.6 --
-    // and loses 5-14 % to the four-column register path between 2:1 and 4:1)
-    // ... and, since its output rows run in a software pipeline and its waves store together, down to 64 outputs per strip (ratios up
-    // to 4) wherever no output row needs more than the pipeline's eight source rows: 3:1 at 270 degrees 300 -> 242 us per 4 images,
-    // 2.5:1 351 -> 271, 2:1 285 -> 275 (profiles/r03_axis_tile.txt)
-    const bool tileable = a.transposed && a.tapStep <= 1 && (a.outStrideB == 1 || a.outStrideB == -1) && a.maxOutputsPerStrip <= 256;
-    const bool tile = tileable && (a.maxOutputsPerStrip > 128 || (a.maxOutputsPerStrip > 64 && a.maxRowSpan <= 8));
-    if (tile && (a.nB + kTileCols - 1) / kTileCols <= 65535) {
+    dim3 grid(shape.gridX, shape.gridY, shape.gridZ), block(kWaves * 64);
+    if (shape.kernel == AXIS_RUN_TILE) {
         // transposed quadrants at ratios below 4: LDS tile, stores along dst x (see aai_axis_tile_kernel)
         if (kernelName) *kernelName = "aai_axis_tile_kernel";
-        dim3 grid(a.nStrips, (a.nB + kWaves * kTileCols - 1) / (kWaves * kTileCols), batch), block(kWaves * 64);
         if (nt) hipLaunchKernelGGL((aai_axis_tile_kernel<true, T>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv);
         else hipLaunchKernelGGL((aai_axis_tile_kernel<false, T>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv);
         return hipGetLastError();
     }
-    int blocksY = (a.nB + rows - 1) / rows;
-    while (blocksY > 65535) { rows *= 2; blocksY = (a.nB + rows - 1) / rows; }
-    dim3 grid((a.nStrips + kWaves - 1) / kWaves, blocksY, batch), block(kWaves * 64);
     if (kernelName) *kernelName = "aai_axis_kernel";
     if (a.tapStep > 1) {
         if (nt) hipLaunchKernelGGL((aai_axis_kernel<true, T, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);

@@ -189,17 +189,11 @@ static aai::AxisLaunch make_axis_launch(const Plan &p, int channels, int64_t dst
     a.maxRowSpan = t.maxRowSpan;
     a.rowsShared = t.rowsShared ? 1 : 0;
     a.maxOutputsPerStrip = t.maxOutputsPerStrip;
-    // (ka,kb) -> dst element: the lane axis is dst x unless the quadrant transposes; flips run an axis
-    // backwards
-    // (with interleaved channels a dst pixel is `channels` elements wide and lane entry ka = pixel * channels + channel)
-    const int nApix = t.nA / channels;
-    const int64_t sa = t.transposed ? dstStride : channels, sb = t.transposed ? channels : dstStride;
-    a.outStrideA = t.flipA ? -sa : sa;
-    a.outStrideB = t.flipB ? -sb : sb;
-    a.outBase = (t.flipA ? (int64_t)(nApix - 1) * sa : 0) + (t.flipB ? (int64_t)(t.nB - 1) * sb : 0);
+    // (ka, kb) -> dst element: axis_out_map (aai_plan.hpp)
+    const aai::AxisOutMap m = aai::axis_out_map(t, channels, dstStride);
+    a.outStrideA = m.outStrideA; a.outStrideB = m.outStrideB; a.outBase = m.outBase;
     a.transposed = t.transposed ? 1 : 0;
-    a.tapStep = channels; a.outChan = channels;
-    if (channels > 1 && !t.transposed && !t.flipA) { a.outStrideA = 1; a.outChan = 1; }     // lane order = dst element order
+    a.tapStep = m.tapStep; a.outChan = m.outChan;
     a.tuneRows = p.tuneRows; a.tuneNt = p.tuneNt;
     return a;
 }

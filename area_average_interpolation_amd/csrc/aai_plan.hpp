@@ -130,6 +130,136 @@ struct AxisTables {
 void build_axis_tables(const Geometry &g, int mode, AxisTables &t, int channels = 1);
 void restrict_axis_tables_to_band(const Geometry &g, AxisTables &t, int row0, int row1, int &srcRow0, int &srcRow1, int extraRows = 0);
 
+// (ka, kb) -> dst element of K1: outBase + (ka / outChan) * outStrideA + ka % outChan + kb * outStrideB.  The lane axis is dst x unless
+// the quadrant transposes; flips run an axis backwards.  With interleaved channels a dst pixel is `channels` elements
+// wide and lane entry ka = pixel * channels + channel.  dstStride: elements of a dst row.
+struct AxisOutMap {
+    int64_t outBase, outStrideA, outStrideB;
+    int tapStep, outChan;
+};
+inline AxisOutMap axis_out_map(const AxisTables &t, int channels, int64_t dstStride)
+{
+    AxisOutMap m{};
+    const int nApix = t.nA / channels;
+    const int64_t sa = t.transposed ? dstStride : channels, sb = t.transposed ? channels : dstStride;
+    m.outStrideA = t.flipA ? -sa : sa;
+    m.outStrideB = t.flipB ? -sb : sb;
+    m.outBase = (t.flipA ? (int64_t)(nApix - 1) * sa : 0) + (t.flipB ? (int64_t)(t.nB - 1) * sb : 0);
+    m.tapStep = channels; m.outChan = channels;
+    if (channels > 1 && !t.transposed && !t.flipA) { m.outStrideA = 1; m.outChan = 1; }     // lane order = dst element order
+    return m;
+}
+
+// ---- K1: the launch shape (aai_axis.hip: launch_axis_typed launches what axis_launch_shape says) ---------------------------------
+// Stated here, without HIP types, so that the variant probe of the tests (tests/emulation: aai_emu_axis_variant, tests/axis_variants.py)
+// asks the function the launcher asks.
+constexpr int kAxisWaves = 4;          // waves (= strips of the strip kernel) per workgroup
+constexpr int kAxisTileCols = 16;      // output rows (= dst columns) a wave of the tile kernel gathers
+
+enum AxisKernelKind { AXIS_RUN_NOTHING = 0, AXIS_RUN_STRIP = 1, AXIS_RUN_TILE = 2, AXIS_RUN_WIDE = 3 };      // aai_axis_kernel, aai_axis_tile_kernel, aai_axis_wide_kernel
+
+// what the choice reads: fields of AxisLaunch (aai_kernels.hpp) of the same names, the source's element size and the batch
+struct AxisShapeFacts {
+    int nA, nB, nStrips;
+    int wide, maxRowSpan, rowsShared, maxOutputsPerStrip;
+    int transposed, tapStep;
+    int64_t outStrideB;
+    int tuneRows, tuneNt;
+    int elemBytes;               // 4, 2 or 1
+    int batch;
+};
+
+struct AxisShape {
+    int kernel;                  // AxisKernelKind
+    int nt;                      // nontemporal source loads (strip and tile kernels)
+    int rows;                    // output rows per workgroup (strip kernel; the tile kernel's workgroups take kAxisWaves * kAxisTileCols)
+    int tileNR;                  // tile kernel: source rows per pipeline window (axis_tile_window_rows)
+    unsigned gridX, gridY, gridZ;      // strip and tile kernels (the wide kernel: gridX and gridZ; its rows go in launches of 65535 * 4)
+};
+
+// The tile kernel's pipeline: windows of at most four source rows (ratios up to 3) run eight output rows in flight, windows of up to
+// eight rows (ratios up to 4, where a strip still holds more than 64 outputs) four.  Asked by aai_axis_tile_kernel itself.
+AAI_HD constexpr int axis_tile_window_rows(int maxRowSpan) { return maxRowSpan <= 4 ? 4 : 8; }
+
+// Which of its five branches aai_axis_kernel takes for a strip of nOut outputs, in the order of the source.  This RESTATES the five
+// conditions of the if / else chain in aai_axis_kernel (aai_axis.hip) for the tests' variant probe; the kernel keeps its own text,
+// because routing it through this function changes the code the compiler emits for it.  Change both together.
+//   A  transposed quadrants, one output per lane, eight dst columns in registers      B  transposed, up to four outputs per lane, four columns
+//   C  one output per lane      D  four consecutive outputs per lane (dst x along the lanes)      E  lanes walk the outputs
+enum AxisStripBranch { AXIS_BRANCH_A = 0, AXIS_BRANCH_B = 1, AXIS_BRANCH_C = 2, AXIS_BRANCH_D = 3, AXIS_BRANCH_E = 4 };
+AAI_HD constexpr int axis_strip_branch(bool interleaved, int nOut, int64_t outStrideA, int64_t outStrideB)
+{
+    return (!interleaved && nOut <= 64 && (outStrideB == 1 || outStrideB == -1))    ? AXIS_BRANCH_A
+           : (!interleaved && nOut <= 256 && (outStrideB == 1 || outStrideB == -1)) ? AXIS_BRANCH_B
+           : nOut <= 64                                                             ? AXIS_BRANCH_C
+           : (nOut <= 256 && outStrideA == 1)                                       ? AXIS_BRANCH_D
+                                                                                    : AXIS_BRANCH_E;
+}
+
+// Launch shape (see the comment at aai_axis_kernel for the measurements behind the defaults).
+// Defaults from the sweeps in profiles/r01_axis_tune_*.txt (8192^2 sources):
+//   * windows that share source rows between output rows (grid not pixel-aligned) want cached loads and
+//     two rows per workgroup (5.8 vs 5.2 TB/s at 4:1); disjoint windows want nontemporal loads;
+//   * >= 4 source rows per output row: one output row per workgroup (6.8 TB/s at 4:1; 5.3 at 8 rows);
+//   * 2-3 source rows: four (5.0-5.2 TB/s vs 3.7-4.6 at one or two);
+//   * ratios below 2 (129..256 outputs per strip, write-heavy): 32 rows per workgroup (4.2 TB/s at 1:1
+//     vs 2.5 at four and 1.4 at one); the up-sampling path (more than 256 outputs per strip) prefers 4;
+//   * 8- and 16-bit sources move 4x / 2x fewer bytes and are bound by per-wave latency, not by HBM: eight / four
+//     rows per workgroup (8192^2 u8 -> 2048^2: 28 us at one row, 21 at eight; profiles/r01_typed_sources.txt).
+inline AxisShape axis_launch_shape(const AxisShapeFacts &a)
+{
+    AxisShape s{};
+    if (a.nA <= 0 || a.nB <= 0 || a.batch <= 0) return s;
+    s.gridZ = (unsigned)a.batch;
+    if (a.wide) {
+        s.kernel = AXIS_RUN_WIDE;
+        s.gridX = (unsigned)((a.nA + 63) / 64);
+        return s;
+    }
+    int nt = a.rowsShared ? 0 : 1;
+    int rows = a.maxRowSpan >= 4 ? (a.rowsShared ? 2 : 1) : 4;
+    if (a.elemBytes < 4) {
+        // ... as long as that leaves a few workgroups per CU
+        const int want = a.elemBytes == 1 ? 8 : 4;
+        const int64_t stripBlocks = (int64_t)((a.nStrips + kAxisWaves - 1) / kAxisWaves) * a.batch;
+        while (rows < want && stripBlocks * ((a.nB + 2 * rows - 1) / (2 * rows)) >= 2048) rows *= 2;
+    }
+    if (a.transposed) {
+        // transposed quadrants: 2, 4 or 8 dst columns per lane and store; about 16 source rows per workgroup is the
+        // sweet spot between DRAM page locality and store width (8192^2 at 90 degrees: 4:1 5.9 TB/s at 4 rows vs 5.2 at
+        // 8; 8:1 6.0 at 2 vs 4.8 at 8; profiles/r01_axis_transposed.txt)
+        rows = a.maxRowSpan >= 8 ? 2 : (a.maxRowSpan >= 3 ? 4 : 8);
+        if (a.maxOutputsPerStrip > 64) rows = a.maxRowSpan >= 2 ? 4 : 16;     // the four-column path (ratios below 4)
+    }
+    if (!a.transposed && a.maxOutputsPerStrip > 128 && a.maxOutputsPerStrip <= 256) rows = 32;      // ratios below 2: write-heavy
+    // the plan's measured choice for this (geometry, device) -- fp32 sources only (aai_engine.cpp: tune_axis_plan)
+    if (a.elemBytes == 4 && a.tuneRows > 0) { rows = a.tuneRows; nt = a.tuneNt; }
+    s.nt = nt;
+    // The LDS-tile kernel (measured, profiles/r01_axis_transposed.txt: wins below 2:1 -- 1:1 1.8 -> 2.3 TB/s, x4 up-sampling 1.2 -> 1.6 --
+    // and loses 5-14 % to the four-column register path between 2:1 and 4:1)
+    // ... and, since its output rows run in a software pipeline and its waves store together, down to 64 outputs per strip (ratios up
+    // to 4) wherever no output row needs more than the pipeline's eight source rows: 3:1 at 270 degrees 300 -> 242 us per 4 images,
+    // 2.5:1 351 -> 271, 2:1 285 -> 275 (profiles/r03_axis_tile.txt)
+    const bool tileable = a.transposed && a.tapStep <= 1 && (a.outStrideB == 1 || a.outStrideB == -1) && a.maxOutputsPerStrip <= 256;
+    const bool tile = tileable && (a.maxOutputsPerStrip > 128 || (a.maxOutputsPerStrip > 64 && a.maxRowSpan <= 8));
+    if (tile && (a.nB + kAxisTileCols - 1) / kAxisTileCols <= 65535) {
+        // transposed quadrants at ratios below 4: LDS tile, stores along dst x (see aai_axis_tile_kernel); one strip per workgroup
+        s.kernel = AXIS_RUN_TILE;
+        s.rows = kAxisWaves * kAxisTileCols;
+        s.tileNR = axis_tile_window_rows(a.maxRowSpan);
+        s.gridX = (unsigned)a.nStrips;
+        s.gridY = (unsigned)((a.nB + kAxisWaves * kAxisTileCols - 1) / (kAxisWaves * kAxisTileCols));
+        return s;
+    }
+    int blocksY = (a.nB + rows - 1) / rows;
+    while (blocksY > 65535) { rows *= 2; blocksY = (a.nB + rows - 1) / rows; }
+    s.kernel = AXIS_RUN_STRIP;
+    s.rows = rows;
+    s.gridX = (unsigned)((a.nStrips + kAxisWaves - 1) / kAxisWaves);
+    s.gridY = (unsigned)blocksY;
+    return s;
+}
+
 // ---- the transpose of K1 (aai_axis_adjoint.hip) ------------------------------------------------------------
 // Output indices [k0, k1] (inclusive) along one axis whose window holds a given source index; k0 > k1: no dst pixel reads it.
 struct AxisRange { int32_t k0, k1; };

@@ -1454,4 +1454,113 @@ int aai_emu_rot_variant(const aai_request *rq, int channels, int srcElemBytes, i
     return AAI_OK;
 }
 
+// The variant probe of K1 (tests/axis_variants.py): the launch shape axis_launch_shape (aai_plan.hpp) gives launch_axis_typed for a
+// request with `channels` interleaved channels of srcElemBytes bytes each and `batch` images, whole (band0 < 0) or restricted to the
+// dst rows [band0, band1), and what the kernels do with it strip by strip and workgroup by workgroup.  The tables are built as
+// build_plan / make_axis_launch build them (aai_engine.cpp: build_axis_tables, restrict_axis_tables_to_band with the band margin of
+// area / fast requests, axis_out_map with a tight dst row of dW * channels elements; no measured launch shape: tuneRows = 0, which is
+// what every plan below 64 MiB of source, every typed, transposed, banded or interleaved plan has).  The strip branches come from
+// axis_strip_branch, which restates the kernel's chain (see there); the loops over workgroups, waves and lanes below restate the index
+// arithmetic of aai_axis_kernel / aai_axis_tile_kernel (rowStart / rowEnd, the store tails, nq, nCols, kDepth, colc / shift) and
+// nothing of the launch rules.  out[0 .. AXV_COUNT): see the enum.  A request that is not axis-aligned reports AXV_KERNEL = 0.
+enum AxisVariantField {
+    AXV_KERNEL = 0,         // AxisKernelKind: 1 strip (aai_axis_kernel), 2 tile, 3 wide
+    AXV_NT, AXV_ROWS, AXV_TILE_NR,
+    AXV_NSTRIPS, AXV_NA, AXV_NB, AXV_MAX_OUTPUTS, AXV_MAX_ROW_SPAN, AXV_ROWS_SHARED,
+    AXV_TRANSPOSED, AXV_SIGN_A, AXV_SIGN_B, AXV_OUT_CHAN,
+    AXV_BRANCHES,           // strip kernel: bit b set = some strip takes branch b (AxisStripBranch, A = bit 0)
+    AXV_A_ITERS, AXV_A_STORES,      // branch A: iterations of its kb0 loop in a full workgroup; stores that occur: bit 0 = 2 x 16 bytes (8 columns), 1 = 16 bytes, 2 = 8 bytes, 3 = scalar
+    AXV_B_ITERS, AXV_B_STORES,      // branch B: the same; bit 0 = 16 bytes (4 columns), 1 = scalar
+    AXV_TILE_NQ,            // tile kernel: bit (nq - 1) set = some strip has (nOut + 63) / 64 = nq
+    AXV_TILE_NCOLS,         // tile kernel, over the waves: bit 0 nCols == 16, 1 kDepth <= nCols < 16, 2 0 < nCols < kDepth, 3 nCols == 0
+    AXV_TILE_TALL,          // tile kernel: some wave takes the `tall` fall-back of tile_columns
+    AXV_SHIFTS,             // strip and tile kernels: bit s set = some lane parks with shift s (0..3); bit 4 = a lane wholly past the row's end
+    AXV_LAST_WG_SHORT,      // strip kernel: the last workgroup along x has fewer than four strips
+    AXV_MIN_LANE_W, AXV_MIN_ROW_W,  // smallest non-zero weight of the two tables (the bits of a float)
+    AXV_DW, AXV_DH, AXV_GRID_X, AXV_GRID_Y,
+    AXV_B_NQ,               // branch B: bit (nq - 1) set = some strip of it has (nOut + 63) / 64 = nq (2..4: its third and fourth horizontal pass run for nq > 2, > 3)
+    AXV_COUNT
+};
+int aai_emu_axis_variant(const aai_request *rq, int channels, int srcElemBytes, int batch, int band0, int band1, int *out)
+{
+    for (int i = 0; i < AXV_COUNT; ++i) out[i] = 0;
+    Geometry g;
+    std::string msg;
+    const int rc = make_geometry(*rq, g, msg);
+    if (rc != AAI_OK) return rc;
+    out[AXV_DW] = g.dW; out[AXV_DH] = g.dH;
+    if (!g.axisAligned || (rq->mode != AAI_MODE_AREA && rq->mode != AAI_MODE_FAST) || channels < 1 || channels > 4) return AAI_OK;
+    AxisTables t;
+    build_axis_tables(g, rq->mode, t, channels);
+    if (band0 >= 0) {
+        if (band1 <= band0 || band1 > g.dH) return AAI_ERR_BAD_ARGUMENT;
+        int a = 0, b = 0;
+        restrict_axis_tables_to_band(g, t, band0, band1, a, b, 1);
+    }
+    const AxisOutMap m = axis_out_map(t, channels, (int64_t)g.dW * channels);
+    const int nStrips = (int)t.strips.size(), srcW = g.W * channels;
+    const AxisShapeFacts facts{t.nA, t.nB, nStrips, t.wide ? 1 : 0, t.maxRowSpan, t.rowsShared ? 1 : 0, t.maxOutputsPerStrip, t.transposed ? 1 : 0,
+                               m.tapStep, m.outStrideB, 0, 0, srcElemBytes, batch};
+    const AxisShape s = axis_launch_shape(facts);
+    out[AXV_KERNEL] = s.kernel; out[AXV_NT] = s.nt; out[AXV_ROWS] = s.rows; out[AXV_TILE_NR] = s.tileNR;
+    out[AXV_NSTRIPS] = nStrips; out[AXV_NA] = t.nA; out[AXV_NB] = t.nB; out[AXV_MAX_OUTPUTS] = t.maxOutputsPerStrip;
+    out[AXV_MAX_ROW_SPAN] = t.maxRowSpan; out[AXV_ROWS_SHARED] = t.rowsShared ? 1 : 0;
+    out[AXV_TRANSPOSED] = t.transposed ? 1 : 0;
+    out[AXV_SIGN_A] = m.outStrideA < 0 ? -1 : 1; out[AXV_SIGN_B] = m.outStrideB < 0 ? -1 : 1; out[AXV_OUT_CHAN] = m.outChan;
+    out[AXV_GRID_X] = (int)s.gridX; out[AXV_GRID_Y] = (int)s.gridY;
+    auto min_weight = [](const std::vector<AxisEntry> &tab) {
+        float w = 0.f;
+        for (const AxisEntry &e : tab) {
+            const float c[3] = {e.wFirst, e.s1 - e.s0 > 1 ? e.wMid : 0.f, e.s1 > e.s0 ? e.wLast : 0.f};      // (the weights some tap carries)
+            for (float v : c)
+                if (v > 0.f && (w == 0.f || v < w)) w = v;
+        }
+        int bits;
+        std::memcpy(&bits, &w, sizeof bits);
+        return bits;
+    };
+    out[AXV_MIN_LANE_W] = min_weight(t.lane); out[AXV_MIN_ROW_W] = min_weight(t.row);
+    if (s.kernel != AXIS_RUN_STRIP && s.kernel != AXIS_RUN_TILE) return AAI_OK;
+    // park(): col = x0 + 4 lane, colc = min(col, srcW - 4), shift = col - colc
+    for (const AxisStrip &st : t.strips)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int col = st.x0 + 4 * lane, shift = col - std::min(col, srcW - 4);
+            out[AXV_SHIFTS] |= 1 << std::min(shift, 4);
+        }
+    if (s.kernel == AXIS_RUN_STRIP) {
+        out[AXV_LAST_WG_SHORT] = nStrips % kAxisWaves != 0;
+        int branches = 0;
+        for (const AxisStrip &st : t.strips) {
+            const int b = axis_strip_branch(m.tapStep > 1, st.k1 - st.k0, m.outStrideA, m.outStrideB);
+            branches |= 1 << b;
+            if (b == AXIS_BRANCH_B) out[AXV_B_NQ] |= 1 << ((st.k1 - st.k0 + 63) / 64 - 1);
+        }
+        out[AXV_BRANCHES] = branches;
+        const int full = std::min(s.rows, t.nB);
+        if (branches & (1 << AXIS_BRANCH_A)) out[AXV_A_ITERS] = (full + 7) / 8;
+        if (branches & (1 << AXIS_BRANCH_B)) out[AXV_B_ITERS] = (full + 3) / 4;
+        for (int by = 0; by < (int)s.gridY; ++by) {
+            const int rowStart = by * s.rows, rowEnd = std::min(rowStart + s.rows, t.nB);
+            if (branches & (1 << AXIS_BRANCH_A))
+                for (int kb0 = rowStart; kb0 < rowEnd; kb0 += 8)
+                    out[AXV_A_STORES] |= kb0 + 8 <= rowEnd ? 1 : kb0 + 4 == rowEnd ? 2 : kb0 + 2 == rowEnd ? 4 : 8;
+            if (branches & (1 << AXIS_BRANCH_B))
+                for (int kb0 = rowStart; kb0 < rowEnd; kb0 += 4)
+                    out[AXV_B_STORES] |= kb0 + 4 <= rowEnd ? 1 : 2;
+        }
+        return AAI_OK;
+    }
+    const int NR = s.tileNR, kDepth = NR == 4 ? 8 : 4;      // tile_columns<NT, T, 4, 8> / <NT, T, 8, 4>
+    for (const AxisStrip &st : t.strips) out[AXV_TILE_NQ] |= 1 << ((st.k1 - st.k0 + 63) / 64 - 1);
+    for (int by = 0; by < (int)s.gridY; ++by)
+        for (int wave = 0; wave < kAxisWaves; ++wave) {
+            const int kb0 = (by * kAxisWaves + wave) * kAxisTileCols;
+            const int nCols = std::max(0, std::min(kAxisTileCols, t.nB - kb0));
+            out[AXV_TILE_NCOLS] |= nCols == kAxisTileCols ? 1 : nCols >= kDepth ? 2 : nCols > 0 ? 4 : 8;
+            for (int j = 0; j < nCols; ++j)
+                if (t.row[kb0 + j].s1 - t.row[kb0 + j].s0 >= NR) out[AXV_TILE_TALL] = 1;
+        }
+    return AAI_OK;
+}
+
 }  // extern "C"

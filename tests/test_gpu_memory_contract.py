@@ -22,10 +22,12 @@ rules of aai_axis.hip (a strip = 256 source elements; nOut = outputs per strip; 
   transposed, 8-column stores    90 / 270 degrees, nOut <= 64.  rows = 8 needs windows of at most two source rows, i.e. a NARROW
                                  image at ratio 1: 50 / 51 / 53 x nB with nB = 16 (8 + 8), 12 (8 + 4), 10 (8 + 2), 11 (8 + scalar);
                                  at 4:1 rows = 4 (the 4-store tail alone), at 8:1 rows = 2 (the 2-store tail alone)
-  transposed, 4-column stores    NOT REACHABLE through the C ABI: it needs 65..256 outputs per strip (a ratio below 4) in a launch
-                                 the LDS-tile kernel does not take, and launch_axis_typed gives the tile kernel every such launch whose
-                                 windows are at most 8 source rows tall -- with equal x and y resolutions (aai_query refuses others) a
-                                 ratio below 4 never has taller ones.  Those geometries run here and land in aai_axis_tile_kernel.
+  transposed, 4-column stores    not reached here: it needs 65..256 outputs per strip (a ratio below 4) in a launch the LDS-tile kernel
+                                 does not take.  launch_axis_typed gives the tile kernel every such launch whose windows are at most 8
+                                 source rows tall -- with equal x and y resolutions (aai_query refuses others) a ratio below 4 never has
+                                 taller ones -- UNLESS the tile kernel's grid cannot carry it: more than 1,048,560 output columns at
+                                 90 / 270 degrees (65,535 groups of 16).  A 100 x 1,048,600 source at 1:1 and 270 degrees lands in this
+                                 branch; tests/test_axis_variants_gpu.py runs it.  The geometries below land in aai_axis_tile_kernel.
 """
 import ctypes
 import os

@@ -541,6 +541,14 @@ int enqueue(const aai_request &rq, const aai::Geometry &g, int batch, const void
             float *d0 = dDst + (int64_t)b0 * dstImageStride;
             const int nb = std::min(batch - b0, kMaxGridZ);
             e = aai::launch_axis(a, s0, srcType, sv, d0, dv, nb, stream, &name);
+            // dst rows and columns off the image: 0 whatever the source holds (K1 multiplies a parked window by weights of 0).
+            // Integer sources have no value whose product with 0 is not 0.
+            if (srcType == aai::SRC_F32) {
+                for (size_t i = 0; i < p->tabs.emptyRow.size() && e == hipSuccess; ++i)
+                    e = aai::launch_axis_zero(a, 0, a.nA, p->tabs.emptyRow[i].k0, p->tabs.emptyRow[i].k1, d0, dv, nb, stream);
+                for (size_t i = 0; i < p->tabs.emptyLane.size() && e == hipSuccess; ++i)
+                    e = aai::launch_axis_zero(a, p->tabs.emptyLane[i].k0, p->tabs.emptyLane[i].k1, 0, a.nB, d0, dv, nb, stream);
+            }
             // dst pixels where the reference's classifier departs from the separable model (aai_axis_verify.hpp)
             if (e == hipSuccess && p->flaggedPixels) {
                 aai::launch_rotated_fixup(r, nb, s0, srcType, sv, d0, dv, static_cast<const uint2 *>(p->dList), p->flaggedPixels, stream);

@@ -48,6 +48,8 @@ struct AxisLaunch {
 };
 hipError_t launch_axis(const AxisLaunch &a, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, hipStream_t stream, const char **kernelName);
+// 0 into the dst pixels of output indices [ka0, ka1) x [kb0, kb1): the rows and columns of empty table entries, behind launch_axis
+hipError_t launch_axis_zero(const AxisLaunch &a, int ka0, int ka1, int kb0, int kb1, float *dst, ImageView dv, int batch, hipStream_t stream);
 
 // ---- K2/K3/K4/K5: per-output-pixel kernels on the rotated lattice --------------------------------------
 // Flagged dst pixels (geometry only), found once per plan: one 64-bit lane mask per wave of the 16x16-pixel tiling.

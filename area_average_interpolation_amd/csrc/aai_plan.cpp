@@ -378,6 +378,9 @@ AxisEntry fold(const VirtRange &vr, int m, int scale, bool reversed, double othe
         if (vb == b && !(a == b)) w += wb - 1;
         return w;
     };
+    // (every tap of a non-empty window gets a positive weight -- a and b are pixels the range overlaps or holds the centre of -- so the
+    // only products with 0 that K1 forms are those of the all-zero entries, which launch_axis_zero overwrites; the replay's
+    // aai_emu_axis_invariants checks it)
     e.s0 = t0; e.s1 = t1;
     e.wFirst = (float)(weight(t0) / total);
     e.wLast = (t1 > t0) ? (float)(weight(t1) / total) : 0.f;
@@ -426,6 +429,17 @@ static void build_axis_strips(AxisTables &t, int srcRowElements)
     }
 }
 
+void axis_empty_runs(const std::vector<AxisEntry> &tab, std::vector<AxisRun> &runs)
+{
+    runs.clear();
+    const int n = (int)tab.size();
+    for (int k = 0; k < n; ++k) {
+        if (tab[k].wFirst != 0.f || tab[k].wMid != 0.f || tab[k].wLast != 0.f) continue;
+        if (!runs.empty() && runs.back().k1 == k) runs.back().k1 = k + 1;
+        else runs.push_back(AxisRun{k, k + 1});
+    }
+}
+
 // Derived data of a (possibly band-restricted) pair of tables: parked empties, row statistics, strips.
 static void finalize_axis_tables(const Geometry &g, AxisTables &t)
 {
@@ -444,6 +458,8 @@ static void finalize_axis_tables(const Geometry &g, AxisTables &t)
         if (t.row[i].wMid + t.row[i].wFirst > 0.f && t.row[i + 1].wMid + t.row[i + 1].wFirst > 0.f && t.row[i].s1 >= t.row[i + 1].s0) { t.rowsShared = true; break; }
 
     build_axis_strips(t, g.W * (t.channels > 1 ? t.channels : 1));
+    axis_empty_runs(t.lane, t.emptyLane);
+    axis_empty_runs(t.row, t.emptyRow);
 }
 
 void build_axis_tables(const Geometry &g, int mode, AxisTables &t, int channels)
@@ -500,6 +516,7 @@ void build_axis_tables(const Geometry &g, int mode, AxisTables &t, int channels)
         t.nA = (int)t.lane.size();
         t.channels = channels;
         build_axis_strips(t, g.W * channels);      // (t.channels is set: strips break on pixel boundaries)
+        axis_empty_runs(t.lane, t.emptyLane);
     }
 }
 

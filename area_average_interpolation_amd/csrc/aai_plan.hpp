@@ -108,6 +108,9 @@ static_assert(sizeof(AxisEntry) == 32, "AxisEntry layout");
 // A wave strip: output indices [k0,k1) along the lane axis whose windows all lie in [x0, x0+STRIP_COLS).
 struct alignas(16) AxisStrip { int32_t k0, k1, x0, pad; };
 
+// Output indices [k0, k1) along one axis whose entries are all empty (weights 0: dst pixels off the image)
+struct AxisRun { int32_t k0, k1; };
+
 constexpr int STRIP_COLS = 256;   // 64 lanes x float4
 
 struct AxisTables {
@@ -124,7 +127,12 @@ struct AxisTables {
     bool rowsShared = false;         // consecutive output rows read a common source row (windows not pixel-aligned)
     int maxOutputsPerStrip = 0;
     int channels = 1;                // interleaved channels: the lane table has nA = pixels * channels entries, taps `channels` apart
+    // Maximal runs of empty entries (as a rule the first and the last few of a table, when the canvas overhangs the image).  K1 multiplies
+    // the parked window of such an entry by its weights of 0, which is 0 for finite data only: the launcher stores 0 into these rows and
+    // columns behind K1 (launch_axis_zero), so that a NaN or Inf at the parked position stays where it is.
+    std::vector<AxisRun> emptyLane, emptyRow;
 };
+void axis_empty_runs(const std::vector<AxisEntry> &tab, std::vector<AxisRun> &runs);
 
 // mode: AAI_MODE_AREA (overlap lengths) or AAI_MODE_FAST (centre counts).  Only for g.axisAligned.
 void build_axis_tables(const Geometry &g, int mode, AxisTables &t, int channels = 1);

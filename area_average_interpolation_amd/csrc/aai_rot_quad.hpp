@@ -549,6 +549,37 @@ AAI_HD bool quad_pixel(const QuadConsts<F> &q, int Xc, int Yc, double dfx, doubl
 #pragma unroll
         for (int c = 0; c < NC; ++c) sumVA[c] = qfma(w, vals[c], sumVA[c]);
     };
+    // The same for a pixel an edge cuts, whose area can come out exactly 0 (a pair that only touches): it must then contribute nothing,
+    // whatever its value -- 0 x NaN would put a source pixel's NaN into a dst pixel it does not overlap.  The select sits behind a vote
+    // on the values, like the cell formulation's (aai_rot_cell.hpp, `add`): finite values take the plain product, whose bits it keeps.
+    // EXCEPTION: the parts of a wide window (PART: aai_wide_kernel) keep the plain product, so a zero-area pair there still carries
+    // 0 x NaN.  Their cut passes run lane by lane over the set bits; the vote made aai_wide_kernel 3.6 % slower at 8:1 and a bare
+    // compare-and-select 1.2 % (profiles/value_domain.txt), and a slower kernel does not ship.  include/aai.h names the exception;
+    // tests/value_domain.py (NOT_LOCAL_CASES) holds the expected failure.
+    auto accumulate_cut = [&](F w, int slot) {
+        F vals[NC];
+        if (SCAN) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) vals[c] = F(1);
+        } else src.at(slot, vals);
+        if (PART) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) sumVA[c] = qfma(w, vals[c], sumVA[c]);
+            return;
+        }
+        bool ok = true;
+        if (!SCAN) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) ok = ok && qabs(vals[c]) <= F(3.0e38);
+        }
+        if (SCAN || AAI_WAVE_ALL(ok)) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) sumVA[c] = qfma(w, vals[c], sumVA[c]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) sumVA[c] = qfma(w, w != F(0) ? vals[c] : F(0), sumVA[c]);
+        }
+    };
     // window origin: first pixel centre the square's bounding box can reach
     const F fi0 = floor(fpx - q.hbm) + (PART ? (F)(partI * WIN) : F(0)), fj0 = floor(fpy - q.hbm) + (PART ? (F)(partJ * WIN) : F(0));
     const int i0 = (int)fi0, j0 = (int)fj0;
@@ -668,7 +699,7 @@ AAI_HD bool quad_pixel(const QuadConsts<F> &q, int Xc, int Yc, double dfx, doubl
             if (valid & bit) {
                 const F area = quad_vertex_area(q, fx, fy, vtx);
                 sumA += area;
-                accumulate(area, slot);
+                accumulate_cut(area, slot);
             }
         }
     } else {
@@ -693,7 +724,7 @@ AAI_HD bool quad_pixel(const QuadConsts<F> &q, int Xc, int Yc, double dfx, doubl
                 else area = quad_vertex_area(q, (F)fxD, (F)fyD, vtx);
             } else area = quad_vertex_area(q, fx, fy, vtx);
             sumA += area;
-            accumulate(area, slot);
+            accumulate_cut(area, slot);
         }
     }
     }
@@ -743,7 +774,7 @@ AAI_HD bool quad_pixel(const QuadConsts<F> &q, int Xc, int Yc, double dfx, doubl
         }
         const F area = quad_cut_tp(q, tp, flip, isLR && q.ref != 0);
         sumA += area;
-        accumulate(area, slot);
+        accumulate_cut(area, slot);
     }
     // ---- pixels cut by both near edge lines --------------------------------------------------------------------------
     while (mDouble) {
@@ -765,7 +796,7 @@ AAI_HD bool quad_pixel(const QuadConsts<F> &q, int Xc, int Yc, double dfx, doubl
         const F area = quad_double<F, SCAN>(q, A, B, tpA, flipA, tpB, flipB, (a < F(0)) == (b < F(0)), nearS);
         if (SCAN && nearS < q.margin) uncertain = true;
         sumA += area;
-        accumulate(area, slot);
+        accumulate_cut(area, slot);
     }
     if (SCAN && !PART && sumA > F(0) && sumA < q.minArea) uncertain = true;
     return uncertain;

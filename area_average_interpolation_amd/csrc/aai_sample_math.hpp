@@ -11,11 +11,14 @@ AAI_HD void keys(float t, float w[4])
 {
     // Every multiply-add spelled out: the planar fast path and the general path (typed sources, interleaved channels) must
     // round these weights alike, whatever the compiler would fuse in either place.
-    const float a = -0.5f, t2 = t * t, t3 = t2 * t;
-    w[0] = a * (fmaf(-2.f, t2, t3) + t);                                  // a (t^3 - 2 t^2 + t)
-    w[1] = fmaf(a + 2.f, t3, fmaf(-(a + 3.f), t2, 1.f));                  // (a + 2) t^3 - (a + 3) t^2 + 1
-    w[2] = fmaf(-(a + 2.f), t3, fmaf(2.f * a + 3.f, t2, -(a * t)));       // -(a + 2) t^3 + (2 a + 3) t^2 - a t
-    w[3] = a * (t2 - t3);                                                 // a (t^2 - t^3)
+    // In factored form: every weight is a product of terms that fp32 holds to a relative 1e-7, so a weight near its zero (t close to
+    // 0 or 1) keeps its RELATIVE accuracy.  The expanded polynomials cancel there (absolute error 1e-7 on a weight of 1e-5), which
+    // shows as soon as the tap behind such a weight is orders of magnitude larger than its neighbours (tests/value_domain.py).
+    const float a = -0.5f, u = 1.f - t;
+    w[0] = (a * t) * (u * u);                                             // a (t^3 - 2 t^2 + t) = a t (1 - t)^2
+    w[1] = u * fmaf(-1.5f * t, t, 1.f + t);                               // (a + 2) t^3 - (a + 3) t^2 + 1 = (1 - t) (1 + t - 1.5 t^2)
+    w[2] = t * fmaf(-1.5f * u, u, 1.f + u);                               // the same in 1 - t
+    w[3] = (a * u) * (t * t);                                             // a (t^2 - t^3) = a t^2 (1 - t)
 }
 
 // one sample point: integer tap origin, fractions, and whether it lies outside the image extent

@@ -35,6 +35,19 @@ unsigned stride_grid(size_t n)
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
+// Behind K1 (aai_axis.hip), where a table has empty entries (AxisTables::emptyLane / emptyRow, aai_plan.hpp): 0 into the dst pixels
+// (ka, kb) of a rectangle of output indices, at the addresses K1 itself wrote them to.  (It lives here so that K1's own unit, and with
+// it the code object of the measured kernels, stays as it is.)
+__global__ __launch_bounds__(256) void aai_axis_zero_kernel(AxisLaunch a, float *__restrict__ dst, ImageView dv, int ka0, int ka1, int kb0, int kb1)
+{
+    const int ka = ka0 + blockIdx.x * 64 + (threadIdx.x & 63);
+    if (ka >= ka1) return;
+    const int oc = a.outChan > 1 ? a.outChan : 1;
+    float *out = dst + (int64_t)blockIdx.z * dv.imageStride + a.outBase + (int64_t)(ka / oc) * a.outStrideA + ka % oc;
+    for (int kb = kb0 + blockIdx.y * 4 + (threadIdx.x >> 6); kb < kb1; kb += gridDim.y * 4)
+        out[(int64_t)kb * a.outStrideB] = 0.f;
+}
+
 }  // namespace
 
 // rows [row0, row1) of the W x H pattern; dst addresses row row0
@@ -65,6 +78,16 @@ hipError_t launch_f32_to_f64(const float *src, double *dst, size_t n, hipStream_
 {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(aai_f32_to_f64_kernel, dim3(stride_grid(n)), dim3(256), 0, stream, src, dst, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_axis_zero(const AxisLaunch &a, int ka0, int ka1, int kb0, int kb1, float *dst, ImageView dv, int batch, hipStream_t stream)
+{
+    ka0 = ka0 > 0 ? ka0 : 0; ka1 = ka1 < a.nA ? ka1 : a.nA; kb0 = kb0 > 0 ? kb0 : 0; kb1 = kb1 < a.nB ? kb1 : a.nB;
+    if (ka0 >= ka1 || kb0 >= kb1 || batch <= 0) return hipSuccess;
+    const int blocksY = (kb1 - kb0 + 3) / 4;
+    dim3 grid((ka1 - ka0 + 63) / 64, blocksY < 65535 ? blocksY : 65535, batch);
+    hipLaunchKernelGGL(aai_axis_zero_kernel, grid, dim3(256), 0, stream, a, dst, dv, ka0, ka1, kb0, kb1);
     return hipGetLastError();
 }
 

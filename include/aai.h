@@ -142,6 +142,18 @@ int aai_device_count(int *count);
 int aai_set_device(int ordinal);          /* one process per GPU: call once with LOCAL_RANK */
 int aai_device_synchronize(void);
 
+/* ---- what the values may be ---------------------------------------------------------------------------
+ * Every mode is LINEAR in the pixel values, out = sum w_i v_i, for data of either sign: a dst pixel is within 1e-5 of the
+ * magnitude-weighted average, |out - exact| <= 1e-5 max(sum |w_i| |v_i|, 1e-3 max|v|), for magnitudes up to 1e30 (beyond that
+ * the fp32 sums of value x area over a window can overflow).  A non-finite source pixel (NaN, +Inf, -Inf) reaches exactly the
+ * dst pixels that have a non-zero weight on it, and every other dst pixel keeps the bits it has with that pixel at 0: a dst
+ * pixel off the image is 0 whatever the source holds, and a pair that merely touches carries nothing.  The samplers
+ * (AAI_MODE_BILINEAR / AAI_MODE_BICUBIC) blend their whole clamped 2 x 2 / 4 x 4 tap window, so there a non-finite pixel
+ * reaches at most the dst pixels whose window holds it, a tap of weight 0 included.  EXCEPTION: the fp32 area kernel for
+ * footprints wider than one 8 x 8 window (aai_wide_kernel, ratios from about 5.5:1 at general rotations) may also put NaN
+ * into a dst pixel that only touches the poisoned pixel (area exactly 0); AAI_POLICY_DOUBLE_PRECISION does not.  Held by
+ * tests/value_domain.py against the CPU oracle for every kernel family. */
+
 /* ---- resampling: host buffers ------------------------------------------------------------------------
  * Replaces the whole call at Source.cpp:1565 / 1569 for callers that hold the image in host memory:
  * upload, run the hot path on the GPU, download.  `dst` must hold layout.dst_height rows of

@@ -126,6 +126,18 @@ AAI_HD double pair_area(const RotLaunch &f, double lx, double ly, int policy, bo
 
 static float row_w(const AxisEntry &e, int y) { return y == e.s0 ? e.wFirst : (y == e.s1 ? e.wLast : e.wMid); }
 
+// launch_axis_zero behind K1 (enqueue, csrc/aai_engine.cpp): 0 into the rows and columns of the tables' empty entries
+template <typename At>
+static void emu_axis_zero(const AxisTables &t, At &&at)
+{
+    for (const AxisRun &r : t.emptyRow)
+        for (int kb = r.k0; kb < r.k1; ++kb)
+            for (int ka = 0; ka < t.nA; ++ka) at(ka, kb) = 0.f;
+    for (const AxisRun &r : t.emptyLane)
+        for (int ka = r.k0; ka < r.k1; ++ka)
+            for (int kb = 0; kb < t.nB; ++kb) at(ka, kb) = 0.f;
+}
+
 static void emu_axis(const Geometry &g, int mode, const float *src, int64_t srcStride, float *dst, int64_t dstStride)
 {
     AxisTables t;
@@ -145,6 +157,7 @@ static void emu_axis(const Geometry &g, int mode, const float *src, int64_t srcS
                 }
                 dst[base + ka * strideA + kb * strideB] = acc;
             }
+        emu_axis_zero(t, [&](int ka, int kb) -> float & { return dst[base + ka * strideA + kb * strideB]; });
         return;
     }
     std::vector<float> line(STRIP_COLS);
@@ -170,6 +183,7 @@ static void emu_axis(const Geometry &g, int mode, const float *src, int64_t srcS
             }
         }
     }
+    emu_axis_zero(t, [&](int ka, int kb) -> float & { return dst[base + ka * strideA + kb * strideB]; });
 }
 
 // Interleaved channels through the axis-aligned path (mirrors enqueue() in csrc/aai_engine.cpp and the CH = true kernel):
@@ -232,6 +246,7 @@ static int emu_axis_channels(const Geometry &g, int mode, int C, const float *sr
                 dst[out_off(k) + (int64_t)kb * strideB] = s;
             }
         }
+    emu_axis_zero(t, [&](int ka, int kb) -> float & { return dst[out_off(ka) + (int64_t)kb * strideB]; });
     return 0;
 }
 
@@ -1319,6 +1334,9 @@ int aai_emu_axis_invariants(const aai_request *rq)
         if (e.wFirst < 0.f || e.wMid < 0.f || e.wLast < 0.f) return false;
         const double total = (double)e.wFirst + (e.s1 > e.s0 ? (double)e.wLast + (double)e.wMid * (e.s1 - e.s0 - 1) : 0.0);
         const bool empty = e.wFirst == 0.f && e.wMid == 0.f && e.wLast == 0.f;
+        // every tap of a non-empty window has a positive weight: K1 multiplies every tap it loads, and only the windows whose weights are
+        // ALL zero get their 0 from launch_axis_zero (a lone zero-weight tap would carry 0 x NaN)
+        if (!empty && (!(e.wFirst > 0.f) || (e.s1 > e.s0 && !(e.wLast > 0.f)) || (e.s1 > e.s0 + 1 && !(e.wMid > 0.f)))) return false;
         return empty || std::fabs(total - 1.0) < 1e-5;
     };
     for (const auto &en : t.lane) if (!entry_ok(en, g.W)) return 2;

@@ -1105,7 +1105,7 @@ def test_cell_kernel_equals_its_cpu_replay_bit_for_bit(gpu, hostemu, po):
         gpu.debug_cell_min_waves(-1)
 
 
-def test_a_nan_source_pixel_stays_local(gpu):
+def test_a_nan_source_pixel_stays_local(gpu, po):
     """A NaN (or Inf) in the source reaches exactly the dst pixels whose footprint overlaps that pixel: a pair with area 0 must not
     carry 0 x NaN into a dst pixel it does not touch (the cell kernel feeds four dst pixels from every pair, and its fast path for
     finite values is taken by a vote over the wave).  Every fp32 formulation, fast mode, up- and down-sampling."""
@@ -1127,6 +1127,9 @@ def test_a_nan_source_pixel_stays_local(gpu):
                 rc3, _, out_delta, _, _ = gpu.resample_host(delta, sr, dr, iso, ang, mode=mode)
                 assert rc == 0 and rc2 == 0 and rc3 == 0, msg
                 touched = out_delta > 0
+                # (and the mask is the oracle's, not only the device's own: tests/value_domain.py holds every family to that)
+                seen = po.oracle_run(po.MODE_EXACT if mode == 1 else po.MODE_FAST, delta.astype(np.float64), sr, dr, iso, ang).dst != 0
+                assert np.array_equal(touched, seen), (W, sr, ang, mode, kernel, int(touched.sum()), int(seen.sum()))
                 broken = ~np.isfinite(out_bad)
                 assert touched.any() and np.array_equal(broken, touched), (W, sr, ang, mode, kernel, int(touched.sum()), int(broken.sum()))
                 assert np.array_equal(out_bad[~broken], out_zero[~broken]), (W, sr, ang, mode, kernel)

@@ -130,6 +130,15 @@ SAMPLE_ADJOINT_SYMBOLS = {
     "aai_adjoint_sample_interleaved_f32": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
 }
 
+# the extension header include/aai_f64.h: the reference-precision path, double images end to end (the argument lists of
+# aai_resample_batch_device_f32, aai_resample_f64, aai_adjoint_batch_device_f32, aai_adjoint_f32)
+F64_SYMBOLS = {
+    "aai_resample_batch_device_f64": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_resample_exact_f64": (ctypes.c_int, [_RQ, _P, _I64, _P, _I64, _LY]),
+    "aai_adjoint_batch_device_f64": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_adjoint_f64": (ctypes.c_int, [_RQ, _P, _I64, _P, _I64, _LY]),
+}
+
 _lib = None
 
 
@@ -152,7 +161,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()) + list(INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(ROTATED_ADJOINT_SYMBOLS.items()) + list(ROTATED_INTERLEAVED_ADJOINT_SYMBOLS.items()) +
-                                  list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items()) + list(SAMPLE_ADJOINT_SYMBOLS.items())):
+                                  list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items()) + list(SAMPLE_ADJOINT_SYMBOLS.items()) + list(F64_SYMBOLS.items())):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

@@ -451,6 +451,74 @@ def adjoint_sample_interleaved_host(gdst, src_shape, src_resolution, dst_resolut
     return _adjoint_host(True, False, g, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, kind="sample")
 
 
+def resample_device_f64(request, src_ptr, src_stride, dst_ptr, dst_stride, stream=0, batch=None, src_image_stride=0, dst_image_stride=0):
+    """aai_resample_batch_device_f64 (include/aai_f64.h): the area / fast forward on device-resident DOUBLE images, never rounded to fp32 --
+    the reference's own precision.  Raw device pointers (ints), strides in elements (doubles), a hipStream_t handle; every element of
+    the output is written.  No plan, nothing to prepare: the call only enqueues, the first call of a geometry included, and can be
+    captured.  Single-channel; bilinear / bicubic requests raise AaiError."""
+    rc = L.load().aai_resample_batch_device_f64(_ref(request), 1 if batch is None else int(batch), src_ptr, src_stride, src_image_stride,
+                                                dst_ptr, dst_stride, dst_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def adjoint_device_f64(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None, dst_image_stride=0, src_image_stride=0):
+    """aai_adjoint_batch_device_f64 (include/aai_f64.h): gsrc = W(request)^T gdst on device-resident DOUBLE images -- the transpose of
+    what resample_device_f64 computes, pair by pair with the same weight bits; adjoint_device's two passes without its final fp32
+    rounding.  Raw device pointers (ints), strides in elements (doubles), a hipStream_t handle; every element of the src_width x
+    src_height gradient image is written.  No plan: the call only enqueues and can be captured."""
+    rc = L.load().aai_adjoint_batch_device_f64(_ref(request), 1 if batch is None else int(batch), gdst_ptr, dst_stride, dst_image_stride,
+                                               gsrc_ptr, src_stride, src_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def resample_exact_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
+    """Host-buffer reference-precision forward (aai_resample_exact_f64): src is a float64 [H, W] image (anything else is converted to
+    float64), the result float64 and never rounded to fp32 on the way -- resample_host on a float64 image converts to fp32 on the
+    device and widens the fp32 result.  Area and fast modes.  The bits of resample_device_f64.
+
+    Returns (code, message, dst float64 ndarray or None, (dstIsoX, dstIsoY) or None, Layout or None)."""
+    lib = L.load()
+    a = np.asarray(src)
+    if a.ndim != 2:
+        if a.size != 0:
+            raise ValueError("src must be a 2-D image [H, W]")
+        a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    H, W = a.shape
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None, None, None
+    dst = np.empty((lay.dst_height, lay.dst_width), dtype=np.float64)
+    out_lay = L.Layout()
+    rc = lib.aai_resample_exact_f64(_ref(rq), a.ctypes.data, W, dst.ctypes.data, max(lay.dst_width, 1), ctypes.byref(out_lay))
+    if rc != L.OK:
+        return rc, last_error(), None, None, None
+    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+
+
+def adjoint_exact_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
+    """Host-buffer reference-precision adjoint (aai_adjoint_f64): gdst is the float64 [dH, dW] gradient with respect to the output of
+    resample_exact_host(src of shape src_shape = (H, W), ...); returns (code, message, gsrc [H, W] float64 or None).  The bits of
+    adjoint_device_f64."""
+    lib = L.load()
+    H, W = int(src_shape[0]), int(src_shape[1])
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None
+    g = np.ascontiguousarray(gdst, dtype=np.float64)
+    if g.shape != (lay.dst_height, lay.dst_width):
+        raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width),))
+    gsrc = np.empty((H, W), dtype=np.float64)
+    rc = lib.aai_adjoint_f64(_ref(rq), g.ctypes.data, max(lay.dst_width, 1), gsrc.ctypes.data, max(W, 1), None)
+    if rc != L.OK:
+        return rc, last_error(), None
+    return rc, "", gsrc
+
+
 def resample_multi_device(request, shards, src_stride, src_image_stride, dst_stride, dst_image_stride):
     """aai_resample_batch_multi_device_f32: `shards` is a list of (device, count, src_ptr, dst_ptr, stream) -- one batch of
     independent images spread over several GPUs of this process, no collective."""
@@ -537,12 +605,15 @@ def synth_device(dst_ptr, width, height, stride, seed, stream=0):
 class AreaAverageInterpolation:
     """Stateless, like the reference class (no data members, Source.cpp:52-54)."""
 
-    def __init__(self, policy=L.POLICY_REFERENCE):
+    def __init__(self, policy=L.POLICY_REFERENCE, exact=False):
+        """exact=True: areaAverageInterpolation and fastAreaAverageInterpolation run in the reference's own precision (resample_exact_host:
+        double images end to end, dst is float64 whatever src's dtype); the two sampler methods are unchanged."""
         self.policy = policy
+        self.exact = bool(exact)
 
     def _call(self, mode, src, srcResolution, dstResolution, srcIsocenter, rotationAngle):
-        rc, msg, dst, iso, _ = resample_host(src, srcResolution, dstResolution, srcIsocenter, rotationAngle,
-                                             mode=mode, policy=self.policy)
+        host = resample_exact_host if self.exact and mode in (L.MODE_AREA, L.MODE_FAST) else resample_host
+        rc, msg, dst, iso, _ = host(src, srcResolution, dstResolution, srcIsocenter, rotationAngle, mode=mode, policy=self.policy)
         if rc in (L.ERR_RESOLUTION_MISMATCH, L.ERR_RESOLUTION_NONPOSITIVE, L.ERR_NO_ROWS, L.ERR_NO_COLUMNS):
             return (False, msg), None, None          # the reference's {false, message}
         if rc != L.OK:

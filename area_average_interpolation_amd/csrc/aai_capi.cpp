@@ -24,6 +24,7 @@
 #include "../../include/aai_adjoint_rotated_interleaved.h"
 #include "../../include/aai_adjoint_planned_interleaved.h"
 #include "../../include/aai_adjoint_sample.h"
+#include "../../include/aai_f64.h"
 
 using namespace aai::engine;
 
@@ -304,6 +305,21 @@ int adjoint_host(AdjointFamily family, bool interleaved, const aai_request *req,
     return finish(*req, g, layout);
 }
 
+// ---- the reference-precision path (include/aai_f64.h) ----------------------------------------------------------------------
+// The forward's argument checks: those of check_adjoint for a single-channel general adjoint, check for check, in its order and with
+// its messages where they apply (the adjoint entries of aai_f64.h run check_adjoint itself).
+int check_f64_forward(const aai_request *rq, int batch, const void *src, int64_t srcStride, const void *dst, int64_t dstStride, aai::Geometry &g)
+{
+    AAI_TRY(check_request(rq));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(request_geometry(*rq, g));
+    if (rq->mode == AAI_MODE_BILINEAR) return fail(AAI_ERR_BAD_ARGUMENT, "No f64 forward for AAI_MODE_BILINEAR: the area and fast modes only.");
+    if (rq->mode == AAI_MODE_BICUBIC) return fail(AAI_ERR_BAD_ARGUMENT, "No f64 forward for AAI_MODE_BICUBIC: the area and fast modes only.");
+    if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the f64 forward.");
+    AAI_TRY(check_pointers(src, dst));
+    return check_strides(g, 1, srcStride, dstStride);
+}
+
 }  // namespace
 
 extern "C" {
@@ -482,6 +498,64 @@ int aai_adjoint_batch_device_f32(const aai_request *req, int32_t batch,
 int aai_adjoint_f32(const aai_request *req, const float *gdst, int64_t dst_stride, float *gsrc, int64_t src_stride, aai_layout *layout)
 {
     return adjoint_host(ADJOINT_GENERAL, false, req, 1, gdst, dst_stride, gsrc, src_stride, layout);
+}
+
+int aai_resample_batch_device_f64(const aai_request *req, int32_t batch, const double *d_src, int64_t src_stride, int64_t src_image_stride,
+                                  double *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_f64_forward(req, batch, d_src, src_stride, d_dst, dst_stride, g));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue_f64_forward(*req, g, batch, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_resample_exact_f64(const aai_request *req, const double *src, int64_t src_stride, double *dst, int64_t dst_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_f64_forward(req, 1, src, src_stride, dst, dst_stride, g));
+    AAI_TRY(require_device());
+    const size_t nSrc = (size_t)g.W * g.H, nDst = (size_t)g.dW * g.dH;
+    if (!nDst) return finish(*req, g, layout);
+    DeviceBuffer dSrc, dDst;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dSrc.alloc(sizeof(double) * nSrc));
+    AAI_HIP(dDst.alloc(sizeof(double) * nDst));
+    AAI_HIP(upload(dSrc, src, src_stride, g.W, g.H, sizeof(double)));
+    AAI_TRY(enqueue_f64_forward(*req, g, 1, dSrc.as<const double>(), g.W, 0, dDst.as<double>(), g.dW, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    AAI_HIP(download(dst, dst_stride, dDst, g.dW, g.dH, sizeof(double)));
+    return finish(*req, g, layout);
+}
+
+int aai_adjoint_batch_device_f64(const aai_request *req, int32_t batch, const double *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
+                                 double *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint(ADJOINT_GENERAL, req, batch, false, 1, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue_f64_adjoint(*req, g, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_adjoint_f64(const aai_request *req, const double *gdst, int64_t dst_stride, double *gsrc, int64_t src_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint(ADJOINT_GENERAL, req, 1, false, 1, gdst, dst_stride, gsrc, src_stride, g));
+    AAI_TRY(require_device());
+    DeviceBuffer dGdst, dGsrc;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dGdst.alloc(sizeof(double) * (size_t)g.dW * g.dH));
+    AAI_HIP(dGsrc.alloc(sizeof(double) * (size_t)g.W * g.H));
+    AAI_HIP(upload(dGdst, gdst, dst_stride, g.dW, g.dH, sizeof(double)));
+    AAI_TRY(enqueue_f64_adjoint(*req, g, 1, dGdst.as<const double>(), g.dW, 0, dGsrc.as<double>(), g.W, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    AAI_HIP(download(gsrc, src_stride, dGsrc, g.W, g.H, sizeof(double)));
+    return finish(*req, g, layout);
 }
 
 int aai_adjoint_prepare(const aai_request *req) { return adjoint_prepare(ADJOINT_PLANNED, req); }

@@ -608,8 +608,9 @@ static int adjoint_scratch_pool(int device, hipMemPool_t *out)
 // (stream-ordered: hipMallocFromPoolAsync / hipFreeAsync on `stream`; imageBytes == 0: none, n == nullptr), the batch in chunks of
 // chunk_images(), and launch(nb, gd, gs, n) -> hipError_t for the nb images of a chunk at gd / gs.  A launch error is reported under
 // `name`, which the launchers may set; the scratch is freed whatever the launches returned.  aai_last_kernel(): name, "+listed" appended.
-template <typename Launch>
-static int for_each_adjoint_chunk(int batch, const float *dGdst, int64_t dstImageStride, float *dGsrc, int64_t srcImageStride, size_t imageBytes,
+// T: the images' element type (float: every fp32 family; double: the reference-precision adjoint, enqueue_f64_adjoint), deduced.
+template <typename T, typename Launch>
+static int for_each_adjoint_chunk(int batch, const T *dGdst, int64_t dstImageStride, T *dGsrc, int64_t srcImageStride, size_t imageBytes,
                                   int device, hipStream_t stream, const char *&name, bool listed, Launch launch)
 {
     const int chunk = chunk_images(batch, imageBytes);
@@ -850,6 +851,35 @@ int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry 
         return e;
     };
     return for_each_adjoint_chunk(batch, dGdst, dstImageStride, dGsrc, srcImageStride, imageBytes, device, stream, name, listed, launch);
+}
+
+// ---- the reference-precision path (include/aai_f64.h, aai_f64.hip): no plan, no lock, nothing blocks
+int enqueue_f64_forward(const aai_request &rq, const Geometry &g, int batch, const double *dSrc, int64_t srcStride, int64_t srcImageStride, double *dDst,
+                        int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
+{
+    const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
+    const aai::ImageView sv{srcStride, srcImageStride}, dv{dstStride, dstImageStride};
+    const char *name = "";
+    hipError_t e = hipSuccess;
+    for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridZ)
+        e = aai::launch_f64_forward(r, std::min(batch - b0, kMaxGridZ), dSrc + (int64_t)b0 * srcImageStride, sv, dDst + (int64_t)b0 * dstImageStride, dv,
+                                    stream, &name);
+    g_lastKernel = name;
+    if (e != hipSuccess) return hip_fail(e, name);
+    return AAI_OK;
+}
+
+int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, const double *dGdst, int64_t dstStride, int64_t dstImageStride, double *dGsrc,
+                        int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+{
+    int device = 0;
+    AAI_HIP(hipGetDevice(&device));
+    const aai::RotLaunch r = aai::make_rot_launch(g, rq.mode, rq.policy);
+    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
+    const size_t imageBytes = (size_t)g.dW * (size_t)g.dH * sizeof(double);      // pass 1's image, per image in flight
+    const char *name = "";
+    auto launch = [&](int nb, const double *gd, double *gs, double *n) -> hipError_t { return aai::launch_f64_adjoint(r, nb, gd, dv, n, gs, sv, stream, &name); };
+    return for_each_adjoint_chunk(batch, dGdst, dstImageStride, dGsrc, srcImageStride, imageBytes, device, stream, name, false, launch);
 }
 
 int require_device()

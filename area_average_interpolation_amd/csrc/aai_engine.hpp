@@ -212,5 +212,13 @@ enum AdjointFamily { ADJOINT_GENERAL, ADJOINT_PLANNED, ADJOINT_ROTATED, ADJOINT_
 int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
                     int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 
+// The reference-precision path (include/aai_f64.h; the caller has checked the arguments): double images, single-channel, area / fast
+// modes.  No plan, no lock, nothing blocks: the launches of aai_f64.hip on `stream`, the batch split at kMaxGridZ (forward) or in chunks
+// of chunk_images() with the adjoint's stream-ordered scratch (for_each_adjoint_chunk).  Strides in elements.
+int enqueue_f64_forward(const aai_request &rq, const Geometry &g, int batch, const double *dSrc, int64_t srcStride, int64_t srcImageStride, double *dDst,
+                        int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
+int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, const double *dGdst, int64_t dstStride, int64_t dstImageStride, double *dGsrc,
+                        int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
+
 }  // namespace engine
 }  // namespace aai

@@ -185,4 +185,13 @@ hipError_t launch_synth_rows(float *dst, int W, int H, int row0, int row1, int64
 hipError_t launch_f64_to_f32(const double *src, float *dst, size_t n, hipStream_t stream);
 hipError_t launch_f32_to_f64(const float *src, double *dst, size_t n, hipStream_t stream);
 
+// ---- the reference-precision path (aai_f64.hip): DOUBLE images end to end, area / fast modes, every angle, no plan ------
+// forward dst = W src with the weights of aai_adjoint_math.hpp (aai_f64_math.hpp); every dst element written.  `batch` <= 65535.
+hipError_t launch_f64_forward(const RotLaunch &r, int batch, const double *src, ImageView sv, double *dst, ImageView dv, hipStream_t stream,
+                              const char **kernelName);
+// adjoint gsrc = W^T gdst: launch_adjoint's two passes without its final fp32 rounding; n = scratch of batch x dH x dW doubles.
+// `batch` <= 65535.
+hipError_t launch_f64_adjoint(const RotLaunch &r, int batch, const double *gdst, ImageView dv, double *n, double *gsrc, ImageView sv,
+                              hipStream_t stream, const char **kernelName);
+
 }  // namespace aai

@@ -7,7 +7,8 @@ aai_adjoint_planned_batch_device_f32; ``"any"``: aai_adjoint_rotated_batch_devic
 ``"any"`` plus aai_adjoint_rotated_interleaved_device_f32 for channels_last tensors at general rotations; ``"channels_last"``:
 ``"interleaved"`` plus aai_adjoint_planned_interleaved_device_f32 for channels_last tensors at multiples of 90 degrees).  Both launch on ``torch.cuda.current_stream()`` of the
 tensor's device and only enqueue work.  ``sampler_backward=True`` makes the bilinear / bicubic modes differentiable as well: their backward
-is aai_adjoint_sample_batch_device_f32 (aai_adjoint_sample_interleaved_device_f32 for channels_last tensors).
+is aai_adjoint_sample_batch_device_f32 (aai_adjoint_sample_interleaved_device_f32 for channels_last tensors).  ``f64=True`` is the
+reference-precision operator on float64 tensors (aai_resample_batch_device_f64 / aai_adjoint_batch_device_f64): differentiable to any order.
 
 torch is imported here, not by the package: ``import area_average_interpolation_amd`` works without it.
 """
@@ -149,6 +150,69 @@ class _ResampleInterleaved(torch.autograd.Function):
         return gx, None, None, None
 
 
+class _ResampleF64(torch.autograd.Function):
+    """y = W x on a contiguous float64 (B, H, W) tensor: aai_resample_batch_device_f64.  No plan, nothing to prepare.  Its backward is
+    _AdjointF64, whose backward is this function again: W is linear, so the pair differentiates to any order."""
+
+    @staticmethod
+    def forward(ctx, x, rq, lay):
+        B, H, W = x.shape
+        x = x.contiguous()
+        y = torch.empty((B, lay.dst_height, lay.dst_width), dtype=torch.float64, device=x.device)
+        ctx.rq, ctx.lay = rq, lay
+        if B:
+            with torch.cuda.device(x.device):
+                api.resample_device_f64(rq, x.data_ptr(), W, y.data_ptr(), lay.dst_width, stream=torch.cuda.current_stream().cuda_stream,
+                                        batch=B, src_image_stride=H * W, dst_image_stride=lay.dst_height * lay.dst_width)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        return _AdjointF64.apply(gy, ctx.rq, ctx.lay), None, None
+
+
+class _AdjointF64(torch.autograd.Function):
+    """gx = W^T gy on a float64 (B, dH, dW) tensor: aai_adjoint_batch_device_f64; its backward is _ResampleF64"""
+
+    @staticmethod
+    def forward(ctx, gy, rq, lay):
+        B, dH, dW = gy.shape
+        H, W = rq.src_height, rq.src_width
+        gy = gy.contiguous()
+        gx = torch.empty((B, H, W), dtype=torch.float64, device=gy.device)
+        ctx.rq, ctx.lay = rq, lay
+        if B:
+            with torch.cuda.device(gy.device):
+                api.adjoint_device_f64(rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
+                                       batch=B, dst_image_stride=dH * dW, src_image_stride=H * W)
+        return gx
+
+    @staticmethod
+    def backward(ctx, ggx):
+        return _ResampleF64.apply(ggx, ctx.rq, ctx.lay), None, None
+
+
+def _resample_f64(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy):
+    """resample(..., f64=True): the reference-precision operator on a float64 tensor (include/aai_f64.h)"""
+    if x.dtype != torch.float64:
+        raise TypeError("resample(f64=True) takes a float64 tensor, got %s" % x.dtype)
+    if x.dim() not in (2, 3, 4):
+        raise ValueError("resample() takes a tensor of shape (H, W), (B, H, W) or (B, C, H, W)")
+    if not x.is_cuda:
+        raise ValueError("resample() takes a tensor on a GPU (the library has no CPU path)")
+    if mode not in (L.MODE_AREA, L.MODE_FAST):
+        raise ValueError("resample(f64=True): the area and fast modes only (the bilinear / bicubic comparison paths have no float64 path)")
+    H, W = x.shape[-2], x.shape[-1]
+    rq, lay = _query(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    iso = (lay.dst_iso_x, lay.dst_iso_y)
+    lead = tuple(x.shape[:-2])
+    if 0 in lead:
+        return torch.empty(lead + (lay.dst_height, lay.dst_width), dtype=torch.float64, device=x.device), iso
+    # every rank through the (B, H, W) operator; a 4-D tensor plane by plane (channels_last and other strided input is made contiguous)
+    y = _ResampleF64.apply(x.contiguous().view(-1, H, W), rq, lay)
+    return y.view(lead + (lay.dst_height, lay.dst_width)), iso
+
+
 _NO_SAMPLER_ADJOINT = ("resample(): the bilinear / bicubic comparison paths have no adjoint; detach x or run under torch.no_grad() "
                        "(or pass sampler_backward=True for the samplers' own adjoint)")
 
@@ -195,7 +259,7 @@ def _resample_nchw(x, geometry, mode, policy, planned, sampler_backward=False):
 
 
 def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
-             *positional, sampler_backward=False, planned_backward=False):
+             *positional, sampler_backward=False, f64=False, planned_backward=False):
     """Resample a CUDA/HIP fp32 tensor of shape (H, W), (B, H, W) or (B, C, H, W); returns ``(y, dst_isocenter)`` with y of shape
     (dH, dW), (B, dH, dW) or (B, C, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
     bilinear / bicubic comparison paths are differentiable only with sampler_backward=True, below: without it an x that requires grad
@@ -269,6 +333,15 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     plane c); every other input takes the planar route.  planned_backward is not consulted there, and in the area / fast modes
     sampler_backward has no effect.
 
+    f64: False (the default) -- nothing changes: a float64 tensor raises TypeError.  True -- the reference-precision operator
+    (include/aai_f64.h): x must be a float64 tensor (float32 raises TypeError) on a GPU, of shape (H, W), (B, H, W) or (B, C, H, W); the area and
+    fast modes only (a sampler mode raises ValueError, whether or not x requires grad).  The forward is aai_resample_batch_device_f64,
+    the backward aai_adjoint_batch_device_f64, both on torch.cuda.current_stream(), no value ever rounded to fp32.  The two are
+    autograd Functions that are each other's backward, so the operator differentiates to ANY order and torch.autograd.gradcheck /
+    gradgradcheck pass.  There is no plan: nothing is prepared, the first call of a geometry only enqueues, and the call works inside
+    a stream capture on a geometry never seen before.  A 4-D input always takes the planar route (channels_last and other strided input
+    is made contiguous; y is contiguous).  planned_backward and sampler_backward are not consulted.
+
     B == 0 or C == 0 returns an empty tensor of the output's shape without a launch."""
     # planned_backward keeps its place as the eighth positional argument (*positional holds at most that one); sampler_backward is
     # keyword-only
@@ -278,6 +351,8 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         planned_backward = positional[0]
     if not isinstance(x, torch.Tensor):
         raise TypeError("resample() takes a torch.Tensor")
+    if f64:
+        return _resample_f64(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     if x.dtype != torch.float32:
         raise TypeError("resample() takes a float32 tensor, got %s" % x.dtype)
     if x.dim() not in (2, 3, 4):

@@ -6,24 +6,13 @@
 
 #include "aai_plan.hpp"
 #include "aai_rot_math.hpp"
+#include "aai_rot_serve.hpp"
 
 #include <cstdlib>
 
 namespace aai {
 
-// Image addressing shared by every kernel: element (x,y) of image b is base[b*imageStride + y*rowStride + x].
-// Source element types (AAI_DTYPE_* in include/aai.h).  Outputs are always fp32.
-enum SrcType { SRC_F32 = 0, SRC_U8 = 1, SRC_U16 = 2 };
-
-struct ImageView {
-    int64_t rowStride;
-    int64_t imageStride;
-};
-
-// Small facts the launchers and their *_can_* predicates share, each stated once (host code; no kernel calls these).
-// bytes per element of a source type
-constexpr size_t src_elem_size(int srcType) { return srcType == SRC_U8 ? 1 : srcType == SRC_U16 ? 2 : 4; }
-// (slot_words -- LDS words per window slot of interleaved channels -- lives in aai_rot_quad.hpp, where the CPU replay can ask it too)
+// ImageView, SrcType, src_elem_size, spans_4gib and the *_can_* predicates of the rotated families: aai_rot_serve.hpp (no HIP type in it)
 
 // ---- K1: axis-aligned separable kernel ----------------------------------------------------------------
 struct AxisLaunch {
@@ -73,11 +62,6 @@ struct RotFlags {
 };
 enum RotForm { ROT_FORM_QUAD = 0, ROT_FORM_CELL = 1 };
 size_t rotated_flag_words(const RotLaunch &r);      // waves of the tiling = 64-bit words of the mask array
-// the source image spans 4 GiB and more: unsigned 32-bit byte offsets from its first element no longer reach every pixel
-inline bool spans_4gib(const RotLaunch &r, int srcType, ImageView sv)
-{
-    return (int64_t)r.H * sv.rowStride * (int64_t)src_elem_size(srcType) >= ((int64_t)1 << 32);
-}
 hipError_t launch_knife_scan(const RotLaunch &r, unsigned long long *laneMasks, unsigned *counter, hipStream_t stream);
 // the double-precision fix-up pass over a list of dst pixels (defined in aai_rotated_strict.hip);
 // pixelList == NULL: the whole image (grid as for the production pass, at most 65535 tile rows)
@@ -93,20 +77,16 @@ hipError_t launch_flag_list(const unsigned long long *laneMasks, size_t waves, u
                             hipStream_t stream);
 hipError_t launch_rotated(const RotLaunch &r, const QuadMap &m, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                           int batch, const RotFlags &flags, hipStream_t stream, const char **kernelName);
-bool quad_can_address(const RotLaunch &r, int srcType, ImageView sv);
 hipError_t launch_quad(const RotLaunch &r, const QuadMap &m, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, const unsigned long long *skipMasks, hipStream_t stream, const int *live = nullptr);
 
-int quad_anchor_rows(const RotLaunch &r);      // images of 4 GiB and more: how many source rows apart two lanes of a wave can read
-
 // wide footprints (aai_rotated_wide.hip): the quad formulation over a window split into parts, one lane per part
-bool wide_can_serve(const RotLaunch &r, int srcType, ImageView sv);      // r.chan set; RotLaunch::wide, plain images, area mode
+// (wide_can_serve, cell_can_serve: aai_rot_serve.hpp)
 hipError_t launch_wide_scan(const RotLaunch &r, unsigned long long *laneMasks, unsigned *counter, hipStream_t stream);
 hipError_t launch_wide(const RotLaunch &r, const QuadMap &m, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, const unsigned long long *skipMasks, hipStream_t stream);
 
 // the cell formulation (aai_rotated_cell.hip): one lane per cell of the dst grid, every (dst, src) pair evaluated once
-bool cell_can_serve(const RotLaunch &r, int srcType, ImageView sv);      // r.chan set; plain images below 4 GiB, area mode
 hipError_t launch_cell_scan(const RotLaunch &r, unsigned long long *laneMasks, unsigned *counter, hipStream_t stream);
 hipError_t launch_cell(const RotLaunch &r, const QuadMap &m, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, const unsigned long long *skipMasks, hipStream_t stream);

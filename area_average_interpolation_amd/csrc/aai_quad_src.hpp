@@ -331,8 +331,7 @@ __device__ __forceinline__ float fast_window_value(const RotLaunch &r, const Qua
     return count > 0 ? sum / (float)count : 0.f;                      // Source.cpp:905
 }
 
-// (kQuadBlock = 256 lanes: 16 x 16 dst pixels, the tiling of the scans -- aai_quad_src.hpp)
-constexpr int kQuadMaxChan = 4;
+// (kQuadBlock = 256 lanes: 16 x 16 dst pixels, the tiling of the scans -- aai_quad_src.hpp; kQuadMaxChan = 4: aai_rot_quad.hpp)
 
 // the `chan` (2..4) interleaved fp32 channels of one pixel in ONE load instruction (element-aligned)
 __device__ __forceinline__ void load_channels(const float *p, int chan, float (&v)[kQuadMaxChan])

@@ -147,6 +147,7 @@ AAI_HD constexpr int slot_words(size_t elemSize, int chan) { return elemSize == 
 // aai_quad_multi_kernel stages win^2 slots of `words` LDS words per lane, i.e. win * win * words KiB per 256-lane block: two
 // workgroups must fit a CU's 160 KiB (quad_can_address keeps wider windows on the double-precision kernels)
 constexpr int kQuadMultiMaxKiB = 80;
+constexpr int kQuadMaxChan = 4;          // interleaved channels per pixel the multi kernels are built for
 AAI_HD constexpr bool quad_multi_fits_lds(int win, int words) { return win * win * words <= kQuadMultiMaxKiB; }
 // Fast mode, one window: does the row-shaped wave (aai_quad_fast_rows_kernel) serve the geometry instead of the 16 x 4 wave?  With
 // replication, and without it while a dst pixel is at most 1.6 source pixels wide (measurements: aai_rotated_quad.hip, launch_quad_win;

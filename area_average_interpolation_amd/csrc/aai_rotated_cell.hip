@@ -605,45 +605,15 @@ AAI_CELL_ENTRY(launch_cell_multi_u16, unsigned short) { return launch_cell_multi
 #undef AAI_CELL_ENTRY
 
 #if !defined(AAI_CELL_PART) || AAI_CELL_PART == 1
-bool cell_can_serve(const RotLaunch &r, int srcType, ImageView sv)
-{
-    // plain images below 4 GiB (lanes address their pixels with unsigned 32-bit byte offsets from the image's first element)
-    if (!r.cell || r.mode != AAI_MODE_AREA) return false;
-    // Small outputs stay on the quad kernel: a cell wave lives for rows + 1 cell rows, and an image of fewer than ~1000 such
-    // waves (about 720 x 720 dst pixels) cannot fill the chip with them -- the reference's own example call (158 x 158 dst
-    // pixels at 5.9 : 1) takes 71 us on 60 cell waves and 36 us on 390 one-shot quad waves.
-    // (AAI_POLICY_PREFER_CELL asks for the cell kernel all the same)
-    if (!r.preferCell && (int64_t)((r.dW + 62) / 63) * ((r.dH + 7) / 8) < 1024) return false;      // (in waves of 63 columns x 8 rows, whatever the wave's shape)
-    const int64_t esz = (int64_t)src_elem_size(srcType);
-    if (r.chan > 1) {
-        // interleaved channels (aai_cell_multi_kernel, 64 x 1 wave): windows whose slots fit 64 KiB of LDS, below 4 GiB
-        if (r.chan > kQuadMaxChan) return false;
-        // Where it wins (tools/interleaved_bench.py, profiles/r04_interleaved.txt): replicated sources of any type (x2 up-sampling of RGB
-        // fp32 at 30 degrees: 1.48 ms against the quad kernel's 2.78) and fp32 pixels (config 3's geometry, RGB: 0.72 against 0.77);
-        // 8- / 16-bit pixels without replication stay on aai_quad_multi_kernel (RGB 8-bit: 0.49 ms there, 0.68 here -- one lane's window
-        // of packed words is unpacked for four dst pixels' sums, and four channels' sums cross lanes and rows)
-        if (esz != 4 && r.scale <= 1 && !r.preferCell) return false;
-        const CellConsts<float> z = make_cell_consts<float>(r.side, r.c, r.s);
-        if (!cell_multi_fits_lds(z.win, slot_words((size_t)esz, r.chan))) return false;
-        return !spans_4gib(r, srcType, sv);
-    }
-    if (!spans_4gib(r, srcType, sv)) return true;
-    // 4 GiB and more: every wave rebases its offsets on its own first source row (aai_cell_kernel, QuadMap::rebaseWaves); the rows one
-    // wave can touch -- 64 cell columns and up to 33 cell rows of `side` lattice points each, plus its windows -- must span less than
-    // 4 GiB, and the 24-bit multiplies of the window addresses need a pitch below 8 MiB
-    const int64_t span = (int64_t)((97.0 * r.side + 24.0) / (r.scale > 0 ? r.scale : 1)) + 2;
-    return sv.rowStride * esz < ((int64_t)1 << 23) && span * sv.rowStride * esz < ((int64_t)1 << 32);
-}
-
+// (cell_can_serve: aai_rot_serve.hpp)
 hipError_t launch_cell(const RotLaunch &r, const QuadMap &map, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, const unsigned long long *skipMasks, hipStream_t stream)
 {
     if (r.dW <= 0 || r.dyEnd <= r.dyBase || batch <= 0) return hipSuccess;
     QuadMap m = map;
     m.anchorRows = 0;
-    m.rebaseWaves = spans_4gib(r, srcType, sv) ? 1 : 0;
+    m.rebaseWaves = cell_map_rebase_waves(r, srcType, sv);
     if (r.chan > 1) {
-        m.rebaseWaves = 0;
         switch (srcType) {
         case SRC_U8: return launch_cell_multi_u8(r, m, static_cast<const unsigned char *>(src), sv, dst, dv, batch, skipMasks, stream);
         case SRC_U16: return launch_cell_multi_u16(r, m, static_cast<const unsigned short *>(src), sv, dst, dv, batch, skipMasks, stream);

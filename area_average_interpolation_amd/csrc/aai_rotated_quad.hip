@@ -436,39 +436,13 @@ AAI_QUAD_ENTRY(launch_quad_u16, unsigned short) { return launch_quad_typed<unsig
 #undef AAI_QUAD_ENTRY
 
 #if !defined(AAI_QUAD_PART) || AAI_QUAD_PART == 1
-// the widest window of source pixels a dst pixel's footprint can touch, per axis
-static int quad_window(const RotLaunch &r) { return (int)floor(2.0 * (r.h * (r.c + r.s) - 0.5 + 1e-5)) + 3; }
-
-// How many source rows apart two lanes of one wave (a 16 x 4 dst tile) can read: their centres differ by at most
-// 15.6 dst pixel sides, each reaches half a window further, plus slack for rounding and clamping.
-int quad_anchor_rows(const RotLaunch &r)
-{
-    return (int)ceil(15.6 * 2.0 * r.h / r.scale) + quad_window(r) + 4;
-}
-
-bool quad_can_address(const RotLaunch &r, int srcType, ImageView sv)
-{
-    // lanes address their pixels with unsigned 32-bit byte offsets from the image's first element -- or, for plain images
-    // of 4 GiB and more, from an anchor row of their wave (quad_anchor_rows)
-    const int win = quad_window(r);
-    if (spans_4gib(r, srcType, sv)) {
-        if (r.chan > 1) return false;
-        if ((int64_t)(2 * quad_anchor_rows(r) + win + 2) * sv.rowStride * (int64_t)src_elem_size(srcType) >= ((int64_t)1 << 32)) return false;
-    }
-    if (r.chan > 1) {
-        // interleaved channels: the staged window (win^2 slots of `words` LDS words per lane) must leave room for two
-        // workgroups per CU
-        if (!quad_multi_fits_lds(win, slot_words(src_elem_size(srcType), r.chan))) return false;
-    }
-    return true;
-}
-
+// (quad_window, quad_anchor_rows, quad_can_address: aai_rot_serve.hpp)
 hipError_t launch_quad(const RotLaunch &r, const QuadMap &map, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, const unsigned long long *skipMasks, hipStream_t stream, const int *live)
 {
     if (r.dW <= 0 || r.dyEnd <= r.dyBase || batch <= 0) return hipSuccess;
     QuadMap m = map;
-    m.anchorRows = spans_4gib(r, srcType, sv) ? quad_anchor_rows(r) : 0;
+    m.anchorRows = quad_map_anchor_rows(r, srcType, sv);
     switch (srcType) {
     case SRC_U8: return launch_quad_u8(r, m, static_cast<const unsigned char *>(src), sv, dst, dv, batch, skipMasks, stream, live);
     case SRC_U16: return launch_quad_u16(r, m, static_cast<const unsigned short *>(src), sv, dst, dv, batch, skipMasks, stream, live);

@@ -271,20 +271,13 @@ AAI_WIDE_ENTRY(launch_wide_u16, unsigned short) { return launch_wide_typed<unsig
 #undef AAI_WIDE_ENTRY
 
 #if !defined(AAI_WIDE_PART) || AAI_WIDE_PART == 1
-bool wide_can_serve(const RotLaunch &r, int srcType, ImageView sv)
-{
-    if (!r.wide || (r.mode != AAI_MODE_AREA && r.mode != AAI_MODE_FAST) || r.chan != 1 || r.scale != 1 || (r.dyBase & 15) != 0) return false;
-    // (tilesX * 16 blocks along grid.x)
-    if ((int64_t)((r.dW + 15) / 16) * 16 > 2147483647ll) return false;
-    return quad_can_address(r, srcType, sv);
-}
-
+// (wide_can_serve: aai_rot_serve.hpp)
 hipError_t launch_wide(const RotLaunch &r, const QuadMap &map, const void *src, int srcType, ImageView sv, float *dst, ImageView dv,
                        int batch, const unsigned long long *skipMasks, hipStream_t stream)
 {
     if (r.dW <= 0 || r.dyEnd <= r.dyBase || batch <= 0) return hipSuccess;
     QuadMap m = map;
-    m.anchorRows = spans_4gib(r, srcType, sv) ? quad_anchor_rows(r) : 0;
+    m.anchorRows = quad_map_anchor_rows(r, srcType, sv);
     switch (srcType) {
     case SRC_U8: return launch_wide_u8(r, m, static_cast<const unsigned char *>(src), sv, dst, dv, batch, skipMasks, stream);
     case SRC_U16: return launch_wide_u16(r, m, static_cast<const unsigned short *>(src), sv, dst, dv, batch, skipMasks, stream);

@@ -38,7 +38,8 @@ extern "C" {
  * non-finite source pixel reaches exactly the dst pixels that carry weight on it.  A batch of any size (split at 65,535 images).
  * aai_last_kernel() names "aai_f64_forward_kernel<area>" / "<fast>" and "aai_f64_adjoint_gather_kernel<area>" / "<fast>".
  * NOT PROVIDED: interleaved channels, row bands, the multi-device entry, a separable kernel for multiples of 90 degrees.  Offsets
- * are 64-bit throughout; sources of 4 GiB and more are not exercised by the test-suite. */
+ * are 64-bit throughout.  EXERCISED: views that span 4 GiB and more (2^29 doubles) through a wide row pitch, on the source side and on
+ * the dst side, forward and adjoint (tests/test_wide_pitch_gpu.py).  NOT EXERCISED: a dense double image of 4 GiB. */
 int aai_resample_batch_device_f64(const aai_request *req, int32_t batch,
                                   const double *d_src, int64_t src_stride, int64_t src_image_stride,
                                   double *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream);

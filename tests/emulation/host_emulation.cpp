@@ -16,6 +16,7 @@
 #include "../../area_average_interpolation_amd/csrc/aai_strict.hpp"
 #include "../../area_average_interpolation_amd/csrc/aai_rot_quad.hpp"
 #include "../../area_average_interpolation_amd/csrc/aai_rot_cell.hpp"
+#include "../../area_average_interpolation_amd/csrc/aai_rot_serve.hpp"
 #include "../../area_average_interpolation_amd/csrc/aai_axis_verify.hpp"
 
 using namespace aai;
@@ -1468,6 +1469,44 @@ int aai_emu_rot_variant(const aai_request *rq, int channels, int srcElemBytes, i
     if (cell) family = multi ? ROTF_CELL_MULTI : ROTF_CELL;
     else if (r.wide && !multi && r.scale == 1) family = fast ? ROTF_WIDE_FAST : ROTF_WIDE;
     else if (r.quad && !(fast && multi) && (!multi || quad_multi_fits_lds(q.winFull, words))) family = multi ? ROTF_QUAD_MULTI : (fast ? ROTF_QUAD_FAST : ROTF_QUAD);
+    out[ROTV_FAMILY] = family;
+    return AAI_OK;
+}
+
+// The variant probe for a source VIEW (tests/wide_pitch.py): the fields of aai_emu_rot_variant for the same request -- the family
+// now decided as rot_form (aai_engine.cpp) and rot_family (aai_rotated.hip) decide it, by the launchers' own predicates
+// cell_can_serve / wide_can_serve / quad_can_address (aai_rot_serve.hpp) on ImageView{srcRowStride, 0}, whose PRECEDENCE is restated
+// here like above and checked against aai_last_kernel() by the GPU suite -- plus the address regime of that view: spans_4gib, the
+// QuadMap's mul24Ok / fastOk (make_quad_map), the anchor rows (quad_map_anchor_rows) or rebased waves (cell_map_rebase_waves) the
+// serving launcher sets, and the plan form.  out[0 .. ROTP_COUNT).  srcRowStride in elements, >= width * channels.
+enum RotPitchedField { ROTP_SPANS_4GIB = ROTV_COUNT, ROTP_MUL24_OK, ROTP_FAST_OK, ROTP_ANCHOR_ROWS, ROTP_REBASE_WAVES, ROTP_FORM, ROTP_COUNT };
+int aai_emu_rot_variant_pitched(const aai_request *rq, int channels, int srcElemBytes, long long srcRowStride, int *out)
+{
+    for (int i = 0; i < ROTP_COUNT; ++i) out[i] = 0;
+    const int rc = aai_emu_rot_variant(rq, channels, srcElemBytes, out);
+    if (rc != AAI_OK) return rc;
+    Geometry g;
+    std::string msg;
+    make_geometry(*rq, g, msg);
+    if (srcRowStride < (long long)g.W * channels) return AAI_ERR_BAD_ARGUMENT;
+    const int srcType = srcElemBytes == 1 ? SRC_U8 : (srcElemBytes == 2 ? SRC_U16 : SRC_F32);
+    const ImageView sv{(int64_t)srcRowStride, 0};
+    RotLaunch r = make_rot_launch(g, rq->mode, rq->policy);
+    r.chan = channels;
+    const QuadMap m = make_quad_map(g, srcRowStride, r.srcRow0, channels, srcElemBytes);
+    out[ROTP_SPANS_4GIB] = spans_4gib(r, srcType, sv) ? 1 : 0;
+    out[ROTP_MUL24_OK] = m.mul24Ok; out[ROTP_FAST_OK] = m.fastOk;
+    if (out[ROTV_FAMILY] == ROTF_NONE) return AAI_OK;           // K1 and the samplers: the view's span and pitch class only
+    const bool fast = rq->mode == AAI_MODE_FAST, multi = channels > 1;
+    const int form = cell_can_serve(r, srcType, sv) ? 1 : 0;    // (ROT_FORM_CELL; rot_form)
+    out[ROTP_FORM] = form;
+    int family = ROTF_FP64;
+    if (form) { family = multi ? ROTF_CELL_MULTI : ROTF_CELL; out[ROTP_REBASE_WAVES] = cell_map_rebase_waves(r, srcType, sv); }
+    else if (wide_can_serve(r, srcType, sv)) { family = fast ? ROTF_WIDE_FAST : ROTF_WIDE; out[ROTP_ANCHOR_ROWS] = quad_map_anchor_rows(r, srcType, sv); }
+    else if (r.quad && (rq->mode == AAI_MODE_AREA || (fast && !multi)) && quad_can_address(r, srcType, sv)) {
+        family = multi ? ROTF_QUAD_MULTI : (fast ? ROTF_QUAD_FAST : ROTF_QUAD);
+        out[ROTP_ANCHOR_ROWS] = quad_map_anchor_rows(r, srcType, sv);
+    }
     out[ROTV_FAMILY] = family;
     return AAI_OK;
 }

@@ -1343,7 +1343,10 @@ def test_sources_larger_than_4_gib(gpu, po):
     K1, a 46,500 x 46,500 one (8.6 GB, 2.16 G elements: past 32-bit element offsets too): K1 streams them, the fp32
     window kernels of the rotated requests (one window per dst pixel, or a window in parts for wide footprints) take their 32-bit
     lane offsets from an anchor row per wave (QuadMap::anchorRows) and the cell kernel rebases every wave on its own first source row
-    (QuadMap::rebaseWaves), in every quadrant.  Sampled row bands against the CPU oracle's rows."""
+    (QuadMap::rebaseWaves), in every quadrant.  Sampled row bands against the CPU oracle's rows.
+    (Dense images, plain fp32, three ratios.  Every family, source type, interleaved images, the 8 MiB pitch, the bounds of
+    cell_can_serve / quad_can_address, destinations and batches of that size, and the adjoints: tests/test_wide_pitch_gpu.py, on small
+    images in wide-pitch views, every pixel against the oracle.)"""
     import torch
     st = torch.cuda.current_stream().cuda_stream
     for (W, H, cases) in ((33000, 33000, ((4.0, 1.0, 0.0, 1, po.MODE_EXACT), (3.0, 1.0, 17.5, 1, po.MODE_EXACT), (3.0, 1.0, 17.5, 2, po.MODE_FAST),

@@ -30,6 +30,7 @@ POLICY_DOUBLE_PRECISION = 0x100      # OR into a policy: general rotations in do
 POLICY_PREFER_CELL = 0x200           # OR into a policy: the cell formulation also for small outputs (a hint)
 POLICY_DIAG_NO_FIXUP = 0x400         # OR into a policy: DIAGNOSTIC, the fix-up pass over the plan's listed pixels is not launched
 DTYPE_F32, DTYPE_U8, DTYPE_U16 = 0, 1, 2
+HALF_F16, HALF_BF16 = 1, 2           # include/aai_half.h: AAI_HALF_F16 / AAI_HALF_BF16, IEEE binary16 / bfloat16 as raw 16-bit elements
 KERNEL_AXIS, KERNEL_ROTATED, KERNEL_FAST, KERNEL_SAMPLE, KERNEL_AXIS_WIDE = 1, 2, 3, 4, 5
 
 
@@ -139,6 +140,13 @@ F64_SYMBOLS = {
     "aai_adjoint_f64": (ctypes.c_int, [_RQ, _P, _I64, _P, _I64, _LY]),
 }
 
+# the extension header include/aai_half.h: fp16 / bf16 images in and out (aai_resample_batch_device_f32's argument list with the element
+# type behind the batch; aai_resample_f32's with it behind the request)
+HALF_SYMBOLS = {
+    "aai_resample_half_batch_device": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_resample_half_host": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
+}
+
 _lib = None
 
 
@@ -161,7 +169,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()) + list(INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(ROTATED_ADJOINT_SYMBOLS.items()) + list(ROTATED_INTERLEAVED_ADJOINT_SYMBOLS.items()) +
-                                  list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items()) + list(SAMPLE_ADJOINT_SYMBOLS.items()) + list(F64_SYMBOLS.items())):
+                                  list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items()) + list(SAMPLE_ADJOINT_SYMBOLS.items()) + list(F64_SYMBOLS.items()) +
+                                  list(HALF_SYMBOLS.items())):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

@@ -519,6 +519,49 @@ def adjoint_exact_host(gdst, src_shape, src_resolution, dst_resolution, src_isoc
     return rc, "", gsrc
 
 
+def resample_half_device(request, src_ptr, src_stride, dst_ptr, dst_stride, half_dtype, stream=0, batch=None, src_image_stride=0, dst_image_stride=0):
+    """aai_resample_half_batch_device (include/aai_half.h): the forward on device-resident fp16 (half_dtype = HALF_F16) or bf16 (HALF_BF16)
+    images, which writes the SAME element type: every source element widened exactly, the forward's fp32 weights and fp32 sums, one
+    rounding to nearest-even.  Raw device pointers (ints), strides in 2-byte elements, a hipStream_t handle.  Single-channel, all four
+    modes.  The plan is resample_device's (prepare(request, 1) prepares this call too); rotations by 0 / 180 degrees in the area / fast
+    modes run one streaming kernel on the half images (last_kernel(): "aai_axis_half_kernel<f16>" / "<bf16>"), everything else widens
+    into fp32 scratch, runs resample_device's launches and narrows ("<fp32 kernel>+widened")."""
+    rc = L.load().aai_resample_half_batch_device(_ref(request), 1 if batch is None else int(batch), int(half_dtype), src_ptr, src_stride, src_image_stride,
+                                                 dst_ptr, dst_stride, dst_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def resample_half_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE, half_dtype=None):
+    """Host-buffer half-precision forward (aai_resample_half_host): src is a [H, W] image of np.float16 (half_dtype HALF_F16, the default
+    for that dtype) or of np.uint16 holding raw bfloat16 bits (HALF_BF16, the default for that dtype); the result has src's dtype.  The
+    bits of resample_half_device.
+
+    Returns (code, message, dst ndarray or None, (dstIsoX, dstIsoY) or None, Layout or None)."""
+    lib = L.load()
+    a = np.asarray(src)
+    if a.dtype not in (np.float16, np.uint16):
+        raise TypeError("resample_half_host takes np.float16 (fp16) or np.uint16 (raw bf16 bits) images, got %s" % a.dtype)
+    if half_dtype is None:
+        half_dtype = L.HALF_F16 if a.dtype == np.float16 else L.HALF_BF16
+    if a.ndim != 2:
+        if a.size != 0:
+            raise ValueError("src must be a 2-D image [H, W]")
+        a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
+    a = np.ascontiguousarray(a)
+    H, W = a.shape
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None, None, None
+    dst = np.empty((lay.dst_height, lay.dst_width), dtype=a.dtype)
+    out_lay = L.Layout()
+    rc = lib.aai_resample_half_host(_ref(rq), int(half_dtype), a.ctypes.data, max(W, 1), dst.ctypes.data, max(lay.dst_width, 1), ctypes.byref(out_lay))
+    if rc != L.OK:
+        return rc, last_error(), None, None, None
+    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+
+
 def resample_multi_device(request, shards, src_stride, src_image_stride, dst_stride, dst_image_stride):
     """aai_resample_batch_multi_device_f32: `shards` is a list of (device, count, src_ptr, dst_ptr, stream) -- one batch of
     independent images spread over several GPUs of this process, no collective."""

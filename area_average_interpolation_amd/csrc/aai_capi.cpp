@@ -25,6 +25,7 @@
 #include "../../include/aai_adjoint_planned_interleaved.h"
 #include "../../include/aai_adjoint_sample.h"
 #include "../../include/aai_f64.h"
+#include "../../include/aai_half.h"
 
 using namespace aai::engine;
 
@@ -320,6 +321,13 @@ int check_f64_forward(const aai_request *rq, int batch, const void *src, int64_t
     return check_strides(g, 1, srcStride, dstStride);
 }
 
+// ---- the half-precision path (include/aai_half.h) --------------------------------------------------------------------------
+int check_half_dtype(int32_t dtype)
+{
+    if (dtype != AAI_HALF_F16 && dtype != AAI_HALF_BF16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown half-precision element type.");
+    return AAI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -555,6 +563,48 @@ int aai_adjoint_f64(const aai_request *req, const double *gdst, int64_t dst_stri
     AAI_TRY(enqueue_f64_adjoint(*req, g, 1, dGdst.as<const double>(), g.dW, 0, dGsrc.as<double>(), g.W, 0, stream));
     AAI_HIP(hipStreamSynchronize(stream));
     AAI_HIP(download(gsrc, src_stride, dGsrc, g.W, g.H, sizeof(double)));
+    return finish(*req, g, layout);
+}
+
+// The checks of aai_resample_batch_device_f32 in its order -- that entry reports its strides from enqueue(), behind the device check, and so
+// does this one -- with the element type where aai_resample_batch_device checks its src_dtype.
+int aai_resample_half_batch_device(const aai_request *req, int32_t batch, int32_t half_dtype, const void *d_src, int64_t src_stride, int64_t src_image_stride,
+                                   void *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_half_dtype(half_dtype));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_pointers(d_src, d_dst));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(check_strides(g, 1, src_stride, dst_stride));
+    AAI_TRY(enqueue_half(*req, g, batch, half_dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+// (a host entry: the checks of aai_resample_host)
+int aai_resample_half_host(const aai_request *req, int32_t half_dtype, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_half_dtype(half_dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_pointers(src, dst));
+    AAI_TRY(check_strides(g, 1, src_stride, dst_stride));
+    AAI_TRY(require_device());
+    const size_t nSrc = (size_t)g.W * g.H, nDst = (size_t)g.dW * g.dH;
+    if (!nDst) return finish(*req, g, layout);
+    DeviceBuffer dSrc, dDst;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dSrc.alloc(sizeof(uint16_t) * nSrc));
+    AAI_HIP(dDst.alloc(sizeof(uint16_t) * nDst));
+    AAI_HIP(upload(dSrc, src, src_stride, g.W, g.H, sizeof(uint16_t)));
+    AAI_TRY(enqueue_half(*req, g, 1, half_dtype, dSrc.p, g.W, 0, dDst.p, g.dW, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    AAI_HIP(download(dst, dst_stride, dDst, g.dW, g.dH, sizeof(uint16_t)));
     return finish(*req, g, layout);
 }
 

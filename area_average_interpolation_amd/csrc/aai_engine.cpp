@@ -882,6 +882,64 @@ int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, con
     return for_each_adjoint_chunk(batch, dGdst, dstImageStride, dGsrc, srcImageStride, imageBytes, device, stream, name, false, launch);
 }
 
+// ---- the half-precision path (include/aai_half.h, aai_half.hip)
+int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride, void *dDst,
+                 int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
+{
+    if (g.dW == 0 || g.dH == 0 || batch == 0) return AAI_OK;
+    // the forward's plan of a packed single-channel fp32 image: the one the forwarding route's launches use, and aai_prepare(req, 1) builds
+    PlanRef p;
+    const int rc = acquire_plan(rq, g, -1, -1, 1, rot_form(rq, g, 1, aai::SRC_F32, (int64_t)g.W), &p, /*onCallerStream*/ true, stream);
+    if (rc != AAI_OK) return rc;
+    const uint16_t *src = static_cast<const uint16_t *>(dSrc);
+    uint16_t *dst = static_cast<uint16_t *>(dDst);
+    const aai::ImageView sv{srcStride, srcImageStride}, dv{dstStride, dstImageStride};
+    hipError_t e = hipSuccess;
+    if (p->kernel == AAI_KERNEL_AXIS && !p->dense && p->flaggedPixels == 0) {
+        // (the tables and the launch block are read-only here: no side stream, no event, hence no lock)
+        const aai::AxisLaunch a = make_axis_launch(*p, 1, dstStride);
+        if (aai::axis_half_can_serve(a)) {
+            const char *name = "";
+            for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridZ)
+                e = aai::launch_axis_half(a, halfType, src + (int64_t)b0 * srcImageStride, sv, dst + (int64_t)b0 * dstImageStride, dv,
+                                          std::min(batch - b0, kMaxGridZ), stream, &name);
+            g_lastKernel = name;
+            if (e != hipSuccess) return hip_fail(e, name);
+            return AAI_OK;
+        }
+    }
+    // forwarding: widen, the fp32 entry's launches, narrow -- the bits of narrow(fp32 entry(widen(src)))
+    const size_t nSrc = (size_t)g.W * (size_t)g.H, nDst = (size_t)g.dW * (size_t)g.dH;
+    const size_t srcBytes = (nSrc * sizeof(float) + 255) & ~(size_t)255, dstBytes = (nDst * sizeof(float) + 255) & ~(size_t)255;
+    const int chunk = chunk_images(batch, srcBytes + dstBytes);
+    hipMemPool_t pool = nullptr;
+    const int rp = adjoint_scratch_pool(p->device, &pool);
+    if (rp != AAI_OK) return rp;
+    char *scratch = nullptr;
+    AAI_HIP(hipMallocFromPoolAsync((void **)&scratch, (srcBytes + dstBytes) * (size_t)chunk, pool, stream));
+    // (dense fp32 images: all the sources of a chunk, then all its outputs)
+    float *s32 = reinterpret_cast<float *>(scratch), *d32 = reinterpret_cast<float *>(scratch + srcBytes * (size_t)chunk);
+    int rl = AAI_OK;
+    const char *what = "aai_half_widen_kernel";
+    for (int b0 = 0; b0 < batch && e == hipSuccess && rl == AAI_OK; b0 += chunk) {
+        const int nb = std::min(batch - b0, chunk);
+        what = "aai_half_widen_kernel";
+        e = aai::launch_half_widen(halfType, src + (int64_t)b0 * srcImageStride, sv, s32, g.W, g.H, nb, stream);
+        if (e != hipSuccess) break;
+        rl = enqueue(rq, g, nb, s32, aai::SRC_F32, g.W, (int64_t)nSrc, d32, g.dW, (int64_t)nDst, stream);
+        if (rl != AAI_OK) break;
+        what = "aai_half_narrow_kernel";
+        e = aai::launch_half_narrow(halfType, d32, dst + (int64_t)b0 * dstImageStride, dv, g.dW, g.dH, nb, stream);
+    }
+    const std::string lastError = g_lastError;      // (of a failed enqueue(): hipFreeAsync below must not replace it)
+    const hipError_t ef = hipFreeAsync(scratch, stream);
+    if (rl != AAI_OK) return fail(rl, lastError);
+    g_lastKernel += "+widened";
+    if (e != hipSuccess) return hip_fail(e, what);
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    return AAI_OK;
+}
+
 int require_device()
 {
     int n = 0;

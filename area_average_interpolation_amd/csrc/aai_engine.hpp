@@ -220,5 +220,16 @@ int enqueue_f64_forward(const aai_request &rq, const Geometry &g, int batch, con
 int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, const double *dGdst, int64_t dstStride, int64_t dstImageStride, double *dGsrc,
                         int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 
+// The half-precision path (include/aai_half.h; the caller has checked the arguments, strides included): fp16 / bf16 images of raw 16-bit
+// elements in, the same type out, single-channel, every mode.  The plan is the forward's own under its single-channel key (built on the
+// caller's stream by the first call, which blocks; aai_prepare(req, 1) builds the same plan).  Two routes, chosen by static facts of the plan:
+//   DIRECT      kernel AXIS, not dense, no listed pixel, the lane axis along dst x (aai::axis_half_can_serve): aai_axis_half_kernel reads the
+//               half image and writes the half image, no scratch, the batch split at kMaxGridZ
+//   FORWARDING  everything else: widen into fp32 scratch, enqueue() -- the code behind aai_resample_batch_device_f32 -- on the scratch, narrow
+//               into the caller's buffer.  Scratch = a dense fp32 source and a dense fp32 output per image in flight, stream-ordered from
+//               the device's pool (for_each_adjoint_chunk's), the batch in chunks of chunk_images().  aai_last_kernel(): "<fp32 name>+widened".
+int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride, void *dDst,
+                 int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
+
 }  // namespace engine
 }  // namespace aai

@@ -174,4 +174,16 @@ hipError_t launch_f64_forward(const RotLaunch &r, int batch, const double *src, 
 hipError_t launch_f64_adjoint(const RotLaunch &r, int batch, const double *gdst, ImageView dv, double *n, double *gsrc, ImageView sv,
                               hipStream_t stream, const char **kernelName);
 
+// ---- the half-precision path (aai_half.hip; body in aai_half_math.hpp): fp16 / bf16 images, the element type in and out ----
+// halfType: aai::HalfType (aai_half_math.hpp) = AAI_HALF_F16 / AAI_HALF_BF16; images of raw 16-bit elements, strides in elements.
+// The direct kernel over K1's tables: whether it serves a launch block (static facts of the plan: not wide, the lane axis along dst x,
+// single-channel, at least four source columns) ...
+bool axis_half_can_serve(const AxisLaunch &a);
+// ... and its launch (hipErrorInvalidValue where it does not).  No scratch.  `batch` <= 65535.
+hipError_t launch_axis_half(const AxisLaunch &a, int halfType, const void *src, ImageView sv, void *dst, ImageView dv, int batch, hipStream_t stream,
+                            const char **kernelName);
+// pitched half images <-> dense fp32 images (W x H elements each, image b at b * W * H).  `batch` <= 65535.
+hipError_t launch_half_widen(int halfType, const void *src, ImageView sv, float *dst, int W, int H, int batch, hipStream_t stream);
+hipError_t launch_half_narrow(int halfType, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream);
+
 }  // namespace aai

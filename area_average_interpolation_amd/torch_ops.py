@@ -9,6 +9,8 @@ aai_adjoint_planned_batch_device_f32; ``"any"``: aai_adjoint_rotated_batch_devic
 tensor's device and only enqueue work.  ``sampler_backward=True`` makes the bilinear / bicubic modes differentiable as well: their backward
 is aai_adjoint_sample_batch_device_f32 (aai_adjoint_sample_interleaved_device_f32 for channels_last tensors).  ``f64=True`` is the
 reference-precision operator on float64 tensors (aai_resample_batch_device_f64 / aai_adjoint_batch_device_f64): differentiable to any order.
+``half=True`` takes float16 / bfloat16 tensors and returns the same dtype (aai_resample_half_batch_device); its backward widens the
+gradient, runs the fp32 adjoint and rounds once.
 
 torch is imported here, not by the package: ``import area_average_interpolation_amd`` works without it.
 """
@@ -94,21 +96,80 @@ class _Resample(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        B, H, W = ctx.src_shape
-        gy = gy.contiguous()
-        if gy.dtype != torch.float32:
-            gy = gy.float()
-        gx = torch.empty((B, H, W), dtype=torch.float32, device=gy.device)
+        return _adjoint_f32(ctx.rq, ctx.src_shape, ctx.planned, gy), None, None, None
+
+
+def _adjoint_f32(rq, src_shape, planned, gy):
+    """gx (fp32, (B, H, W)) = W^T gy for a (B, dH, dW) gradient of any float dtype: the backward of _Resample and, widened, of _ResampleHalf"""
+    B, H, W = src_shape
+    gy = gy.contiguous()
+    if gy.dtype != torch.float32:
+        gy = gy.float()
+    gx = torch.empty((B, H, W), dtype=torch.float32, device=gy.device)
+    if B:
+        dH, dW = gy.shape[1], gy.shape[2]
+        with torch.cuda.device(gy.device):
+            if planned == _SAMPLER:
+                api.adjoint_sample_device(rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
+                                          batch=B, dst_image_stride=dH * dW, src_image_stride=H * W)
+            else:
+                api.adjoint_device(rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
+                                   batch=B, dst_image_stride=dH * dW, src_image_stride=H * W, planned=planned)
+    return gx
+
+
+_HALF_DTYPES = {torch.float16: L.HALF_F16, torch.bfloat16: L.HALF_BF16}
+
+
+class _ResampleHalf(torch.autograd.Function):
+    """y = round(W x) on a contiguous float16 / bfloat16 (B, H, W) tensor: aai_resample_half_batch_device, y in x's dtype.  The plan is the
+    fp32 forward's.  Backward: gy widened to fp32, _Resample's adjoint (planned honoured the same way), the gradient rounded to x's dtype."""
+
+    @staticmethod
+    def forward(ctx, x, rq, lay, planned):
+        B, H, W = x.shape
+        y = torch.empty((B, lay.dst_height, lay.dst_width), dtype=x.dtype, device=x.device)
+        ctx.rq, ctx.src_shape, ctx.planned, ctx.dtype = rq, (B, H, W), planned, x.dtype
         if B:
-            dH, dW = gy.shape[1], gy.shape[2]
-            with torch.cuda.device(gy.device):
-                if ctx.planned == _SAMPLER:
-                    api.adjoint_sample_device(ctx.rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
-                                              batch=B, dst_image_stride=dH * dW, src_image_stride=H * W)
-                else:
-                    api.adjoint_device(ctx.rq, gy.data_ptr(), dW, gx.data_ptr(), W, stream=torch.cuda.current_stream().cuda_stream,
-                                       batch=B, dst_image_stride=dH * dW, src_image_stride=H * W, planned=ctx.planned)
-        return gx, None, None, None
+            with torch.cuda.device(x.device):
+                _ensure_prepared(rq)
+                if planned and planned != _SAMPLER and ctx.needs_input_grad[0]:
+                    _ensure_adjoint_prepared(rq, "rotated" if planned == "any" and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST) else "planned")
+                api.resample_half_device(rq, x.data_ptr(), W, y.data_ptr(), lay.dst_width, _HALF_DTYPES[x.dtype],
+                                         stream=torch.cuda.current_stream().cuda_stream, batch=B, src_image_stride=H * W,
+                                         dst_image_stride=lay.dst_height * lay.dst_width)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return _adjoint_f32(ctx.rq, ctx.src_shape, ctx.planned, gy).to(ctx.dtype), None, None, None
+
+
+def _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, planned, sampler_backward):
+    """resample(..., half=True): float16 / bfloat16 tensors in, the same dtype out (include/aai_half.h)"""
+    if x.dtype not in _HALF_DTYPES:
+        raise TypeError("resample(half=True) takes a float16 or bfloat16 tensor, got %s" % x.dtype)
+    if x.dim() not in (2, 3, 4):
+        raise ValueError("resample() takes a tensor of shape (H, W), (B, H, W) or (B, C, H, W)")
+    if not x.is_cuda:
+        raise ValueError("resample() takes a tensor on a GPU (the library has no CPU path)")
+    H, W = x.shape[-2], x.shape[-1]
+    rq, lay = _query(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    iso = (lay.dst_iso_x, lay.dst_iso_y)
+    lead = tuple(x.shape[:-2])
+    if 0 in lead:
+        return torch.empty(lead + (lay.dst_height, lay.dst_width), dtype=x.dtype, device=x.device), iso
+    sampler = mode not in (L.MODE_AREA, L.MODE_FAST)
+    if x.requires_grad and torch.is_grad_enabled() and sampler and not sampler_backward:
+        raise ValueError(_NO_SAMPLER_ADJOINT)
+    if planned in ("interleaved", "channels_last"):
+        planned = "any"              # the half path has no interleaved route
+    if sampler and sampler_backward:
+        planned = _SAMPLER
+    # every rank through the (B, H, W) operator; a 4-D tensor plane by plane (channels_last and other strided input is made contiguous)
+    y = _ResampleHalf.apply(x.contiguous().view(-1, H, W), rq, lay, planned)
+    return y.view(lead + (lay.dst_height, lay.dst_width)), iso
 
 
 class _ResampleInterleaved(torch.autograd.Function):
@@ -259,7 +320,7 @@ def _resample_nchw(x, geometry, mode, policy, planned, sampler_backward=False):
 
 
 def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
-             *positional, sampler_backward=False, f64=False, planned_backward=False):
+             *positional, sampler_backward=False, f64=False, half=False, planned_backward=False):
     """Resample a CUDA/HIP fp32 tensor of shape (H, W), (B, H, W) or (B, C, H, W); returns ``(y, dst_isocenter)`` with y of shape
     (dH, dW), (B, dH, dW) or (B, C, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
     bilinear / bicubic comparison paths are differentiable only with sampler_backward=True, below: without it an x that requires grad
@@ -342,6 +403,17 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     a stream capture on a geometry never seen before.  A 4-D input always takes the planar route (channels_last and other strided input
     is made contiguous; y is contiguous).  planned_backward and sampler_backward are not consulted.
 
+    half: False (the default) -- nothing changes: a float16 / bfloat16 tensor raises TypeError.  True -- the half-precision operator
+    (include/aai_half.h): x must be a float16 or bfloat16 tensor (float32 raises TypeError) on a GPU, of shape (H, W), (B, H, W) or
+    (B, C, H, W); y has x's dtype.  The forward is aai_resample_half_batch_device on torch.cuda.current_stream(): every element widened
+    exactly, fp32 weights and sums, ONE rounding to x's dtype; rotations by 0 / 180 degrees in the area / fast modes run one streaming
+    kernel on the half tensors, every other request widens into scratch, runs the fp32 forward and narrows.  The plan is the fp32
+    forward's: the first call of a geometry prepares it, and inside a stream capture an unprepared geometry raises RuntimeError.  A 4-D
+    input always takes the planar route (channels_last and other strided input is made contiguous; y is contiguous).  The area and fast
+    modes are differentiable ONCE: the backward widens gy to fp32, runs the fp32 adjoint with planned_backward honoured as for an fp32
+    tensor ("interleaved" and "channels_last" mean "any": there is no interleaved route), and rounds the gradient to x's dtype;
+    bilinear / bicubic with sampler_backward=True likewise.  torch.autocast does not route here by itself.
+
     B == 0 or C == 0 returns an empty tensor of the output's shape without a launch."""
     # planned_backward keeps its place as the eighth positional argument (*positional holds at most that one); sampler_backward is
     # keyword-only
@@ -353,6 +425,9 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         raise TypeError("resample() takes a torch.Tensor")
     if f64:
         return _resample_f64(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    if half:
+        return _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, _normalise_planned(planned_backward),
+                              bool(sampler_backward))
     if x.dtype != torch.float32:
         raise TypeError("resample() takes a float32 tensor, got %s" % x.dtype)
     if x.dim() not in (2, 3, 4):

@@ -147,6 +147,13 @@ HALF_SYMBOLS = {
     "aai_resample_half_host": (ctypes.c_int, [_RQ, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
 }
 
+# the extension header include/aai_int.h: u8 / u16 images in and out (aai_resample_interleaved_device's argument list with the element
+# type behind the channels; aai_resample_interleaved_host's likewise)
+INT_SYMBOLS = {
+    "aai_resample_int_batch_device": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_resample_int_host": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
+}
+
 _lib = None
 
 
@@ -170,7 +177,7 @@ def load():
         for name, (res, args) in (list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()) + list(INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(ROTATED_ADJOINT_SYMBOLS.items()) + list(ROTATED_INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items()) + list(SAMPLE_ADJOINT_SYMBOLS.items()) + list(F64_SYMBOLS.items()) +
-                                  list(HALF_SYMBOLS.items())):
+                                  list(HALF_SYMBOLS.items()) + list(INT_SYMBOLS.items())):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

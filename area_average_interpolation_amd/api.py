@@ -562,6 +562,49 @@ def resample_half_host(src, src_resolution, dst_resolution, src_isocenter, rotat
     return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
 
 
+def resample_int_device(request, channels, src_ptr, src_stride, dst_ptr, dst_stride, dtype, stream=0, batch=None, src_image_stride=0, dst_image_stride=0):
+    """aai_resample_int_batch_device (include/aai_int.h): the forward on device-resident 8-bit (dtype = DTYPE_U8) or 16-bit (DTYPE_U16)
+    unsigned images of `channels` = 1..4 interleaved channels, which writes the SAME element type: every source element as its integer
+    value, the forward's fp32 weights and fp32 sums, one conversion -- round to nearest, ties to even, saturate.  Raw device pointers
+    (ints), strides in elements, a hipStream_t handle.  All four modes.  The plan is resample_interleaved_device's (prepare(request,
+    channels) prepares this call too); rotations by 0 / 180 degrees in the area / fast modes run one streaming kernel on the integer
+    images (last_kernel(): "aai_axis_int_kernel<u8>" / "<u16>"), everything else runs resample_interleaved_device's launches into fp32
+    scratch and converts ("<fp32 kernel>+quantized")."""
+    rc = L.load().aai_resample_int_batch_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(dtype), src_ptr, src_stride,
+                                                src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def resample_int_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
+    """Host-buffer integer forward (aai_resample_int_host): src is a [H, W] or [H, W, C] (C = 1..4, interleaved) image of np.uint8 or
+    np.uint16; the result has src's dtype and [dH, dW] or [dH, dW, C] shape.  The bits of resample_int_device.
+
+    Returns (code, message, dst ndarray or None, (dstIsoX, dstIsoY) or None, Layout or None)."""
+    lib = L.load()
+    a = np.asarray(src)
+    if a.dtype not in (np.uint8, np.uint16):
+        raise TypeError("resample_int_host takes np.uint8 or np.uint16 images, got %s" % a.dtype)
+    dtype = L.DTYPE_U8 if a.dtype == np.uint8 else L.DTYPE_U16
+    if a.ndim not in (2, 3):
+        if a.size != 0:
+            raise ValueError("src must be an image [H, W] or [H, W, C]")
+        a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
+    a = np.ascontiguousarray(a)
+    H, W = a.shape[:2]
+    C = a.shape[2] if a.ndim == 3 else 1
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None, None, None
+    dst = np.empty((lay.dst_height, lay.dst_width) + ((C,) if a.ndim == 3 else ()), dtype=a.dtype)
+    out_lay = L.Layout()
+    rc = lib.aai_resample_int_host(_ref(rq), C, dtype, a.ctypes.data, max(W * C, 1), dst.ctypes.data, max(lay.dst_width * C, 1), ctypes.byref(out_lay))
+    if rc != L.OK:
+        return rc, last_error(), None, None, None
+    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+
+
 def resample_multi_device(request, shards, src_stride, src_image_stride, dst_stride, dst_image_stride):
     """aai_resample_batch_multi_device_f32: `shards` is a list of (device, count, src_ptr, dst_ptr, stream) -- one batch of
     independent images spread over several GPUs of this process, no collective."""

@@ -26,6 +26,7 @@
 #include "../../include/aai_adjoint_sample.h"
 #include "../../include/aai_f64.h"
 #include "../../include/aai_half.h"
+#include "../../include/aai_int.h"
 
 using namespace aai::engine;
 
@@ -328,6 +329,13 @@ int check_half_dtype(int32_t dtype)
     return AAI_OK;
 }
 
+// ---- the integer path (include/aai_int.h) ------------------------------------------------------------------------------------
+int check_int_dtype(int32_t dtype)
+{
+    if (dtype != AAI_DTYPE_U8 && dtype != AAI_DTYPE_U16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown integer element type.");
+    return AAI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -605,6 +613,54 @@ int aai_resample_half_host(const aai_request *req, int32_t half_dtype, const voi
     AAI_TRY(enqueue_half(*req, g, 1, half_dtype, dSrc.p, g.W, 0, dDst.p, g.dW, 0, stream));
     AAI_HIP(hipStreamSynchronize(stream));
     AAI_HIP(download(dst, dst_stride, dDst, g.dW, g.dH, sizeof(uint16_t)));
+    return finish(*req, g, layout);
+}
+
+// The checks of aai_resample_interleaved_device in its order -- that entry reports its strides from enqueue(), behind the device check, and
+// so does this one -- with the element type where that entry checks its src_dtype.
+int aai_resample_int_batch_device(const aai_request *req, int32_t batch, int32_t channels, int32_t dtype, const void *d_src, int64_t src_stride,
+                                  int64_t src_image_stride, void *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(check_int_dtype(dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_row_length(g, channels));
+    if (batch > 0 && g.dW > 0 && g.dH > 0) AAI_TRY(check_pointers(d_src, d_dst));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(check_strides(g, channels, src_stride, dst_stride));
+    AAI_TRY(enqueue_int(*req, g, batch, channels, dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+// (a host entry: the checks of aai_resample_interleaved_host)
+int aai_resample_int_host(const aai_request *req, int32_t channels, int32_t dtype, const void *src, int64_t src_stride, void *dst, int64_t dst_stride,
+                          aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(check_int_dtype(dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_pointers(src, dst));
+    AAI_TRY(check_row_length(g, channels));
+    AAI_TRY(check_strides(g, channels, src_stride, dst_stride));
+    AAI_TRY(require_device());
+    const size_t elem = aai::src_elem_size(dtype);
+    const int64_t rowSrc = (int64_t)g.W * channels, rowDst = (int64_t)g.dW * channels;
+    if (!rowDst || !g.dH) return finish(*req, g, layout);
+    DeviceBuffer dSrc, dDst;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dSrc.alloc(elem * (size_t)rowSrc * g.H));
+    AAI_HIP(dDst.alloc(elem * (size_t)rowDst * g.dH));
+    AAI_HIP(upload(dSrc, src, src_stride, rowSrc, g.H, elem));
+    AAI_TRY(enqueue_int(*req, g, 1, channels, dtype, dSrc.p, rowSrc, 0, dDst.p, rowDst, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    AAI_HIP(download(dst, dst_stride, dDst, rowDst, g.dH, elem));
     return finish(*req, g, layout);
 }
 

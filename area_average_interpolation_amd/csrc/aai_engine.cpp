@@ -940,6 +940,60 @@ int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int halfTy
     return AAI_OK;
 }
 
+// ---- the integer path (include/aai_int.h, aai_int.hip)
+int enqueue_int(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
+                void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
+{
+    if (g.dW == 0 || g.dH == 0 || batch == 0) return AAI_OK;
+    // the forward's plan under (request, channels): the one enqueue() takes for this source, and aai_prepare(req, channels) builds
+    PlanRef p;
+    const int rc = acquire_plan(rq, g, -1, -1, channels, rot_form(rq, g, channels, srcType, srcStride), &p, /*onCallerStream*/ true, stream);
+    if (rc != AAI_OK) return rc;
+    const int64_t elem = (int64_t)aai::src_elem_size(srcType);
+    char *dst = static_cast<char *>(dDst);
+    const aai::ImageView sv{srcStride, srcImageStride}, dv{dstStride, dstImageStride};
+    hipError_t e = hipSuccess;
+    if (p->kernel == AAI_KERNEL_AXIS && !p->dense && p->flaggedPixels == 0 && (rq.mode == AAI_MODE_AREA || rq.mode == AAI_MODE_FAST)) {
+        // (the tables and the launch block are read-only here: no side stream, no event, hence no lock)
+        const aai::AxisLaunch a = make_axis_launch(*p, channels, dstStride);
+        if (aai::axis_int_can_serve(a, srcType)) {
+            const char *name = "";
+            for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridZ)
+                e = aai::launch_axis_int(a, srcType, src_at(dSrc, srcType, (int64_t)b0 * srcImageStride), sv, dst + (int64_t)b0 * dstImageStride * elem, dv,
+                                         std::min(batch - b0, kMaxGridZ), stream, &name);
+            g_lastKernel = name;
+            if (e != hipSuccess) return hip_fail(e, name);
+            return AAI_OK;
+        }
+    }
+    // forwarding: the interleaved entry's launches into dense fp32 scratch, one conversion -- the bits of quantize(fp32 entry(src))
+    const int64_t rowDst = (int64_t)g.dW * channels;
+    const size_t nDst = (size_t)rowDst * (size_t)g.dH;
+    const size_t dstBytes = (nDst * sizeof(float) + 255) & ~(size_t)255;
+    const int chunk = chunk_images(batch, dstBytes);
+    hipMemPool_t pool = nullptr;
+    const int rp = adjoint_scratch_pool(p->device, &pool);
+    if (rp != AAI_OK) return rp;
+    char *scratch = nullptr;
+    AAI_HIP(hipMallocFromPoolAsync((void **)&scratch, dstBytes * (size_t)chunk, pool, stream));
+    float *d32 = reinterpret_cast<float *>(scratch);      // (dense fp32 outputs: image b of a chunk at b * nDst)
+    int rl = AAI_OK;
+    for (int b0 = 0; b0 < batch && e == hipSuccess && rl == AAI_OK; b0 += chunk) {
+        const int nb = std::min(batch - b0, chunk);
+        rl = enqueue(rq, g, nb, src_at(dSrc, srcType, (int64_t)b0 * srcImageStride), srcType, srcStride, srcImageStride, d32, rowDst, (int64_t)nDst, stream, -1, -1,
+                     channels);
+        if (rl != AAI_OK) break;
+        e = aai::launch_int_quantize(srcType, d32, dst + (int64_t)b0 * dstImageStride * elem, dv, (int)rowDst, g.dH, nb, stream);
+    }
+    const std::string lastError = g_lastError;      // (of a failed enqueue(): hipFreeAsync below must not replace it)
+    const hipError_t ef = hipFreeAsync(scratch, stream);
+    if (rl != AAI_OK) return fail(rl, lastError);
+    g_lastKernel += "+quantized";
+    if (e != hipSuccess) return hip_fail(e, "aai_int_quantize_kernel");
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    return AAI_OK;
+}
+
 int require_device()
 {
     int n = 0;

@@ -231,5 +231,18 @@ int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, con
 int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride, void *dDst,
                  int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
 
+// The integer path (include/aai_int.h; the caller has checked the arguments, strides included): u8 / u16 images (srcType = SRC_U8 /
+// SRC_U16) of `channels` interleaved channels in, the same type out, every mode.  The plan is the forward's own under the key
+// (request, channels) -- what enqueue() uses for this source, and aai_prepare(req, channels) builds.  Two routes, chosen by static facts:
+//   DIRECT      kernel AXIS, not dense, no listed pixel, the lane axis along dst x, area or fast mode, u16 or more than 64 outputs in some
+//               strip (aai::axis_int_can_serve):
+//               aai_axis_int_kernel reads the integer image and writes the integer image, no scratch, the batch split at kMaxGridZ
+//   FORWARDING  everything else: enqueue() -- which reads u8 / u16 itself -- into dense fp32 output scratch, aai_int_quantize_kernel into
+//               the caller's buffer.  Scratch = a dense fp32 output per image in flight, stream-ordered from the device's pool, the batch
+//               in chunks of chunk_images().  aai_last_kernel(): "<fp32 name>+quantized".
+int enqueue_int(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
+                void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
+
 }  // namespace engine
+
 }  // namespace aai

@@ -186,4 +186,17 @@ hipError_t launch_axis_half(const AxisLaunch &a, int halfType, const void *src, 
 hipError_t launch_half_widen(int halfType, const void *src, ImageView sv, float *dst, int W, int H, int batch, hipStream_t stream);
 hipError_t launch_half_narrow(int halfType, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream);
 
+// ---- the integer path (aai_int.hip; body in aai_int_math.hpp): u8 / u16 images of 1..4 interleaved channels, the element type in and out ----
+// srcType: SRC_U8 or SRC_U16 (aai_rot_serve.hpp) = AAI_DTYPE_U8 / AAI_DTYPE_U16; strides in elements.
+// The direct kernel over K1's tables: whether it serves a launch block (static facts of the plan: not wide, the lane axis along dst x,
+// at most 256 outputs per strip, at least four elements in a source row; 8-bit elements only with more than 64 outputs in some strip:
+// the measured rule of profiles/int_time.txt) ...
+bool axis_int_can_serve(const AxisLaunch &a, int srcType);
+// ... and its launch (hipErrorInvalidValue where it does not).  No scratch.  `batch` <= 65535.
+hipError_t launch_axis_int(const AxisLaunch &a, int srcType, const void *src, ImageView sv, void *dst, ImageView dv, int batch, hipStream_t stream,
+                           const char **kernelName);
+// dense fp32 images (W x H elements each -- W = pixels x channels --, image b at b * W * H) -> pitched integer images: round to nearest
+// even, saturate (int_quantize).  `batch` <= 65535.
+hipError_t launch_int_quantize(int srcType, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream);
+
 }  // namespace aai

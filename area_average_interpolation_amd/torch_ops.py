@@ -172,6 +172,45 @@ def _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_an
     return y.view(lead + (lay.dst_height, lay.dst_width)), iso
 
 
+_INT_DTYPES = {torch.uint8: L.DTYPE_U8}
+if hasattr(torch, "uint16"):
+    _INT_DTYPES[torch.uint16] = L.DTYPE_U16
+
+
+def _resample_int(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy):
+    """resample(..., integer=True): uint8 / uint16 tensors in, the same dtype out (include/aai_int.h); no autograd"""
+    if x.dtype not in _INT_DTYPES:
+        raise TypeError("resample(integer=True) takes a uint8 or uint16 tensor, got %s" % x.dtype)
+    if x.dim() not in (2, 3, 4):
+        raise ValueError("resample() takes a tensor of shape (H, W), (B, H, W) or (B, C, H, W)")
+    if not x.is_cuda:
+        raise ValueError("resample() takes a tensor on a GPU (the library has no CPU path)")
+    if x.dim() == 4 and x.shape[1] > 4:
+        raise ValueError("resample(integer=True) takes at most 4 channels, got %d" % x.shape[1])
+    H, W = x.shape[-2], x.shape[-1]
+    rq, lay = _query(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    iso = (lay.dst_iso_x, lay.dst_iso_y)
+    dH, dW = lay.dst_height, lay.dst_width
+    lead = tuple(x.shape[:-2])
+    x = x.detach()
+    # (B, C, H, W) dense in channels_last with C > 1: the NHWC storage is the library's interleaved layout, nothing is copied
+    interleaved = x.dim() == 4 and x.shape[1] > 1 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+    if interleaved:
+        y = torch.empty(lead + (dH, dW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        images, C = x.shape[0], x.shape[1]
+    else:
+        x = x.contiguous()
+        y = torch.empty(lead + (dH, dW), dtype=x.dtype, device=x.device)
+        images, C = x.numel() // max(H * W, 1), 1
+    if 0 in lead or dH == 0 or dW == 0:
+        return y, iso
+    with torch.cuda.device(x.device):
+        _ensure_prepared(rq, C)
+        api.resample_int_device(rq, C, x.data_ptr(), W * C, y.data_ptr(), dW * C, _INT_DTYPES[x.dtype], stream=torch.cuda.current_stream().cuda_stream,
+                                batch=images, src_image_stride=H * W * C, dst_image_stride=dH * dW * C)
+    return y, iso
+
+
 class _ResampleInterleaved(torch.autograd.Function):
     """(B, C, H, W) dense in torch.channels_last, 2 <= C <= 4: the NHWC storage is the library's interleaved layout, nothing is copied"""
 
@@ -320,7 +359,7 @@ def _resample_nchw(x, geometry, mode, policy, planned, sampler_backward=False):
 
 
 def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
-             *positional, sampler_backward=False, f64=False, half=False, planned_backward=False):
+             *positional, sampler_backward=False, f64=False, half=False, integer=False, planned_backward=False):
     """Resample a CUDA/HIP fp32 tensor of shape (H, W), (B, H, W) or (B, C, H, W); returns ``(y, dst_isocenter)`` with y of shape
     (dH, dW), (B, dH, dW) or (B, C, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
     bilinear / bicubic comparison paths are differentiable only with sampler_backward=True, below: without it an x that requires grad
@@ -414,6 +453,18 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     tensor ("interleaved" and "channels_last" mean "any": there is no interleaved route), and rounds the gradient to x's dtype;
     bilinear / bicubic with sampler_backward=True likewise.  torch.autocast does not route here by itself.
 
+    integer: False (the default) -- nothing changes: a uint8 / uint16 tensor raises TypeError.  True -- the integer operator
+    (include/aai_int.h): x must be a torch.uint8 tensor (or torch.uint16 where this torch has that dtype; float32 raises TypeError) on a
+    GPU, of shape (H, W), (B, H, W) or (B, C, H, W) with C <= 4; y has x's dtype.  The forward is aai_resample_int_batch_device on
+    torch.cuda.current_stream(): every element as its integer value, fp32 weights and sums, ONE conversion -- round to nearest, ties to
+    even, saturate to the range of the dtype; rotations by 0 / 180 degrees in the area / fast modes run one streaming kernel on the
+    integer tensors, every other request runs the fp32 forward into scratch and converts.  A (B, C, H, W) tensor dense in
+    torch.channels_last is read in place as B interleaved images and y is channels_last; a contiguous one with C > 1 runs as B * C
+    single-channel images (other strided input is made contiguous).  The plan is the fp32 forward's for that channel count: the first
+    call of a geometry prepares it, and inside a stream capture an unprepared geometry raises RuntimeError.  There is no autograd
+    (integers carry no gradient): y never requires grad.  integer=True together with half, f64, planned_backward or sampler_backward
+    raises ValueError.
+
     B == 0 or C == 0 returns an empty tensor of the output's shape without a launch."""
     # planned_backward keeps its place as the eighth positional argument (*positional holds at most that one); sampler_backward is
     # keyword-only
@@ -423,6 +474,10 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         planned_backward = positional[0]
     if not isinstance(x, torch.Tensor):
         raise TypeError("resample() takes a torch.Tensor")
+    if integer:
+        if half or f64 or planned_backward is not False or sampler_backward:
+            raise ValueError("resample(integer=True) has no gradient and one element type: it takes none of half, f64, planned_backward, sampler_backward")
+        return _resample_int(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     if f64:
         return _resample_f64(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     if half:

@@ -1,0 +1,521 @@
+// aai_axis_narrow.hip -- the narrow-element paths: images whose elements are narrower than fp32 in, the same element type out.
+//   include/aai_half.h   fp16 / bf16, single-channel
+//   include/aai_int.h    u8 / u16, 1..4 interleaved channels
+//
+//   aai_axis_narrow_kernel<E>   the DIRECT route: K1's streaming form (aai_axis.hip) over the forward plan's cached tables -- strips, lane
+//                               and row entries, the (ka, kb) -> dst element map -- for lane axes that run along dst x (rotations by 0 and
+//                               180 degrees).  It computes no geometry.  A narrow element cuts the source bytes of a kernel that is bound
+//                               by the source read, and the output goes out in the element type: no fp32 image exists anywhere.
+//   aai_narrow_widen_kernel<E>  } the FORWARDING route of every other request (aai_engine.cpp: enqueue_narrow): pitched element image ->
+//   aai_narrow_store_kernel<E>  } dense fp32 scratch (half types only: enqueue() reads u8 / u16 itself), the fp32 entry's own launches,
+//                                 dense fp32 scratch -> pitched element image.
+//
+// Work decomposition of the direct kernel = K1's, because the plan's strips are built for it: wave64, one wave per strip of 256 source
+// ELEMENTS (a row of W x channels of them), four waves (adjacent strips) per workgroup, four elements per lane = ONE 4-byte (u8) or
+// 8-byte (2-byte elements) load per lane and source row, the vertical pass in registers with up to four source rows in flight, the row
+// of vertical sums parked in a per-wave LDS line and re-indexed by OUTPUT element for the horizontal pass, whose taps are `tapStep`
+// elements apart (CH; the single-channel form is compiled without the step).  Waves never synchronise with each other: no workgroup barrier.
+// Two forms of the horizontal pass, chosen per strip (wave-uniform) like K1's branches C and D:
+//   * up to 64 outputs in the strip (ratios of 4 and more): one output per lane; neighbouring lanes exchange their elements through
+//     DPP and the first of them stores them (the type's SmallStore: the four lanes of a quad, or a pair of lanes);
+//   * 65 .. 256 outputs (ratios below 4, 1:1, up-sampling -- a strip never holds more than 256, build_axis_strips): four consecutive
+//     outputs per lane.
+// Stores: where the lane order is the dst element order -- 0 degrees with any channel count (forwards), 180 degrees with one channel
+// (backwards) -- four consecutive elements go out as ONE 4-byte (u8) or 8-byte (2-byte elements) store; the tail of a strip, and 180
+// degrees with channels (pixels run backwards, the channels of a pixel forwards), element by element.  Every store covers only elements
+// its lane computed: nothing is read back, so a dword shared with another wave's strip or with the row padding is never rewritten.
+//
+// What an element type decides (Elem<E>), and nothing else:
+//   u8     v_cvt_f32_ubyte<i> in; round to nearest even, saturate (int_quantize) out; 4-byte packs; channels; quad store
+//   u16    shift / mask and convert in; int_quantize out; 8-byte packs; channels; quad store
+//   f16    v_cvt_f32_f16 in (exact); v_cvt_f16_f32 with the canonical NaN of aai_half_math.hpp out; u16's packs; one channel; pair store
+//   bf16   shift / mask in (the bits ARE the fp32's upper half); f32_to_bf16 out; u16's packs; one channel; pair store
+// (The pair store is measured, profiles/narrow_time.txt: with the quad store the half 4:1 rows took about 0.5-1 us more of 107-117 us.)
+//
+// The arithmetic of an element is aai_half_math.hpp's and aai_int_math.hpp's, operation for operation, and this unit is compiled
+// without contraction: the CPU replays of the tests (tests/emulation/narrow_replay.hpp behind half_emulation.cpp and int_emulation.cpp)
+// give this kernel's bits.
+//
+// Memory: loads start no later than element srcW - 4 (park()'s shift rule of K1) and cover source rows of the window only; stores cover
+// output elements only; nothing assumes more than element alignment of a base pointer or a stride.
+#include "aai_kernels.hpp"
+#include "aai_int_math.hpp"
+
+#include <algorithm>
+
+namespace aai {
+
+namespace {
+
+constexpr int kWaves = kAxisWaves;
+constexpr int VEC = 4;         // source elements per lane and load
+
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));             // dword-aligned 16-byte access
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+// VEC consecutive elements of one row, as loaded and as stored (the element-aligned vector types of Raw<T>, aai_axis.hip)
+template <typename T> struct Pack;
+
+template <> struct Pack<unsigned char> {
+    typedef unsigned int word __attribute__((aligned(1)));
+    unsigned w;
+    template <bool NT> __device__ __forceinline__ void load(const unsigned char *p)
+    {
+        const word *v = reinterpret_cast<const word *>(p);
+        w = NT ? __builtin_nontemporal_load(v) : *v;
+    }
+    // elements e0 .. e3 at p[0] .. p[3]
+    static __device__ __forceinline__ void store(unsigned char *p, unsigned e0, unsigned e1, unsigned e2, unsigned e3)
+    {
+        *reinterpret_cast<word *>(p) = e0 | (e1 << 8) | (e2 << 16) | (e3 << 24);
+    }
+};
+
+template <> struct Pack<unsigned short> {
+    typedef unsigned int word2 __attribute__((ext_vector_type(2), aligned(2)));
+    unsigned w0, w1;
+    template <bool NT> __device__ __forceinline__ void load(const unsigned short *p)
+    {
+        const word2 *v = reinterpret_cast<const word2 *>(p);
+        const word2 x = NT ? __builtin_nontemporal_load(v) : *v;
+        w0 = x.x; w1 = x.y;
+    }
+    static __device__ __forceinline__ void store(unsigned short *p, unsigned e0, unsigned e1, unsigned e2, unsigned e3)
+    {
+        word2 r;
+        r.x = e0 | (e1 << 16); r.y = e2 | (e3 << 16);
+        *reinterpret_cast<word2 *>(p) = r;
+    }
+};
+
+template <typename T, bool PK> struct QuadStore;
+struct PairStore;
+
+// The element policy: storage type, element i of a pack as a float, a float as an element (in the low bits), whether the type has
+// interleaved-channel forms, the store of a strip of at most 64 outputs, the name aai_last_kernel() reports.
+template <int E> struct Elem;
+
+template <> struct Elem<NARROW_U8> {
+    typedef unsigned char T;
+    static constexpr bool kChannels = true;
+    static constexpr const char *kName = "aai_axis_int_kernel<u8>";
+    template <bool PK> using SmallStore = QuadStore<T, PK>;
+    static __device__ __forceinline__ float to_float(const Pack<T> &p, int i) { return (float)((p.w >> (8 * i)) & 255u); }     // v_cvt_f32_ubyte<i>
+    static __device__ __forceinline__ unsigned from_float(float f) { return (unsigned)int_quantize<T>(f); }
+};
+
+template <> struct Elem<NARROW_U16> {
+    typedef unsigned short T;
+    static constexpr bool kChannels = true;
+    static constexpr const char *kName = "aai_axis_int_kernel<u16>";
+    template <bool PK> using SmallStore = QuadStore<T, PK>;
+    static __device__ __forceinline__ float to_float(const Pack<T> &p, int i) { return (float)(((i < 2 ? p.w0 : p.w1) >> (16 * (i & 1))) & 65535u); }
+    static __device__ __forceinline__ unsigned from_float(float f) { return (unsigned)int_quantize<T>(f); }
+};
+
+// fp16: the bits of half_widen / half_narrow<HALF_F16> (aai_half_math.hpp) through v_cvt_f32_f16, which is exact, and v_cvt_f16_f32
+// (round to nearest even, overflow to Inf, subnormals kept) with the header's canonical NaN
+template <> struct Elem<NARROW_F16> {
+    typedef unsigned short T;
+    static constexpr bool kChannels = false;
+    static constexpr const char *kName = "aai_axis_half_kernel<f16>";
+    template <bool PK> using SmallStore = PairStore;
+    static __device__ __forceinline__ float widen(unsigned bits16) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16); }
+    static __device__ __forceinline__ float to_float(const Pack<T> &p, int i)
+    {
+        const unsigned w = i < 2 ? p.w0 : p.w1;
+        return widen((i & 1) ? (w >> 16) : (w & 0xffffu));
+    }
+    static __device__ __forceinline__ unsigned from_float(float f)
+    {
+        const unsigned h = __builtin_bit_cast(unsigned short, (_Float16)f);
+        return f != f ? (((__float_as_uint(f) >> 16) & 0x8000u) | 0x7e00u) : h;
+    }
+};
+
+// bf16: the bits of half_widen / half_narrow<HALF_BF16>, the narrowing in the header's integer form
+template <> struct Elem<NARROW_BF16> {
+    typedef unsigned short T;
+    static constexpr bool kChannels = false;
+    static constexpr const char *kName = "aai_axis_half_kernel<bf16>";
+    template <bool PK> using SmallStore = PairStore;
+    static __device__ __forceinline__ float widen(unsigned bits16) { return __uint_as_float(bits16 << 16); }
+    static __device__ __forceinline__ float to_float(const Pack<T> &p, int i)
+    {
+        const unsigned w = i < 2 ? p.w0 : p.w1;
+        return __uint_as_float((i & 1) ? (w & 0xffff0000u) : (w << 16));
+    }
+    static __device__ __forceinline__ unsigned from_float(float f) { return f32_to_bf16(f); }
+};
+
+// a table entry in registers; `span` = number of taps - 1 (of a lane entry: (s1 - s0) / tapStep, worked out once per strip)
+struct Win { int s0, s1; float wF, wM, wL; };
+
+__device__ __forceinline__ Win load_win(const AxisEntry *__restrict__ tab, int k)
+{
+    typedef int i4 __attribute__((ext_vector_type(4)));
+    const i4 q = reinterpret_cast<const i4 *>(tab)[2 * k];
+    const float wl = reinterpret_cast<const float *>(tab)[8 * k + 4];
+    Win w;
+    w.s0 = q.x; w.s1 = q.y; w.wF = __int_as_float(q.z); w.wM = __int_as_float(q.w); w.wL = wl;
+    return w;
+}
+
+struct Cols { float v[VEC]; };
+
+// Vertical pass of one output row: acc = fma(w(y), src[y][col], acc) over the window's rows in ascending order (half_vertical_step).
+// Up to four source rows are issued together; the window is wave-uniform, so rows past it are neither loaded nor added.
+template <int E, bool NT>
+__device__ __forceinline__ Cols vertical_pass(const typename Elem<E>::T *__restrict__ img, int64_t rowStride, int colc, const Win e)
+{
+    typedef typename Elem<E>::T T;
+    Cols acc;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) acc.v[i] = 0.f;
+    for (int y = e.s0; y <= e.s1; y += 4) {
+        Pack<T> r0, r1, r2, r3;
+        const T *p = img + (int64_t)y * rowStride + colc;
+        const bool h1 = y + 1 <= e.s1, h2 = y + 2 <= e.s1, h3 = y + 3 <= e.s1;
+        r0.template load<NT>(p);
+        r1 = r0; r2 = r0; r3 = r0;
+        if (h1) r1.template load<NT>(p + rowStride);
+        if (h2) r2.template load<NT>(p + 2 * rowStride);
+        if (h3) r3.template load<NT>(p + 3 * rowStride);
+        const float w0 = half_row_weight(e.s0, e.s1, e.wF, e.wM, e.wL, y), w1 = half_row_weight(e.s0, e.s1, e.wF, e.wM, e.wL, y + 1);
+        const float w2 = half_row_weight(e.s0, e.s1, e.wF, e.wM, e.wL, y + 2), w3 = half_row_weight(e.s0, e.s1, e.wF, e.wM, e.wL, y + 3);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc.v[i] = half_vertical_step(acc.v[i], w0, Elem<E>::to_float(r0, i));
+        if (h1) {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc.v[i] = half_vertical_step(acc.v[i], w1, Elem<E>::to_float(r1, i));
+        }
+        if (h2) {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc.v[i] = half_vertical_step(acc.v[i], w2, Elem<E>::to_float(r2, i));
+        }
+        if (h3) {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc.v[i] = half_vertical_step(acc.v[i], w3, Elem<E>::to_float(r3, i));
+        }
+    }
+    return acc;
+}
+
+// K1's park(): the lane's VEC vertical sums into the wave's LDS line (position = element - strip origin).  Near the right image edge a
+// lane loaded the last in-range vector instead of its own (colc = min(col, srcW - VEC), shift = col - colc) and writes only the
+// elements at or right of its own first one.
+__device__ __forceinline__ void park(float *line, int lane, int shift, const Cols &c)
+{
+    if (shift == 0) {
+        const f4 v = {c.v[0], c.v[1], c.v[2], c.v[3]};
+        *reinterpret_cast<f4 *>(line + VEC * lane) = v;
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i)
+            if (i >= shift) line[VEC * lane + i - shift] = c.v[i];
+    }
+}
+
+// one output element from the parked line, converted: +0 (all bits 0 in every type) for an entry without weight (a dst column off the
+// image), whatever the line holds.  c.s1 holds the entry's span (taps - 1), not its last element.
+template <int E, bool CH>
+__device__ __forceinline__ unsigned element(const float *line, const Win c, int x0, int step)
+{
+    if (half_entry_empty(c.wF, c.wM, c.wL)) return 0u;
+    const float s = CH ? int_horizontal_stepped(line, c.s0 - x0, c.s1, step, c.wF, c.wM, c.wL) : half_horizontal(line, c.s0 - x0, c.s1, c.wF, c.wM, c.wL);
+    return Elem<E>::from_float(s);
+}
+
+template <bool CH> __device__ __forceinline__ Win lane_win(const AxisEntry *__restrict__ laneTab, int k, int step)
+{
+    Win c = load_win(laneTab, k);
+    c.s1 = CH ? (c.s1 - c.s0) / step : c.s1 - c.s0;
+    return c;
+}
+
+// The up to four consecutive outputs kq .. kq + n - 1 of one lane into dst row `row` (= out + kb * outStrideB).
+//   PK (the lane order is the dst element order, forwards or backwards): all four as one store, fewer one by one
+//   else (180 degrees with channels): element (ka / outChan) * outStrideA + ka % outChan each, worked out once per strip (Scatter)
+struct Scatter { int o[4]; };       // element offsets within a dst row: below 2^30 (check_row_length)
+
+__device__ __forceinline__ Scatter make_scatter(const AxisLaunch &a, int kq)
+{
+    Scatter s;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const int ka = kq + i; s.o[i] = (ka / a.outChan) * (int)a.outStrideA + ka % a.outChan; }
+    return s;
+}
+
+template <typename T, bool PK>
+__device__ __forceinline__ void store_outputs(T *row, const Scatter &sc, bool fwd, int kq, int n, unsigned e0, unsigned e1, unsigned e2, unsigned e3)
+{
+    if (n <= 0) return;
+    if (PK) {
+        T *o = row + (fwd ? (int64_t)kq : -(int64_t)kq);
+        if (n == 4) {
+            if (fwd) Pack<T>::store(o, e0, e1, e2, e3);
+            else Pack<T>::store(o - 3, e3, e2, e1, e0);
+        } else {
+            const int64_t sA = fwd ? 1 : -1;
+            o[0] = (T)e0;
+            if (n > 1) o[sA] = (T)e1;
+            if (n > 2) o[2 * sA] = (T)e2;
+        }
+    } else {
+        row[sc.o[0]] = (T)e0;
+        if (n > 1) row[sc.o[1]] = (T)e1;
+        if (n > 2) row[sc.o[2]] = (T)e2;
+        if (n > 3) row[sc.o[3]] = (T)e3;
+    }
+}
+
+// The store of a strip of at most 64 outputs, one output per lane (lane = ka - k0): set up once per strip, then one call per output row
+// with the lane's element; every lane of the wave calls it (the exchange is a DPP move).
+//   QuadStore: the quad's first lane stores the quad's elements, n of which exist, like a lane of the other form stores its four
+template <typename T, bool PK> struct QuadStore {
+    int kq, n;
+    bool fwd;
+    Scatter sc;
+    __device__ __forceinline__ QuadStore(const AxisLaunch &a, int k0, int k1, int lane, bool fwd_) : fwd(fwd_)
+    {
+        kq = k0 + (lane & ~3);
+        n = (lane & 3) == 0 ? min(max(k1 - kq, 0), 4) : 0;
+        sc = PK ? Scatter{} : make_scatter(a, kq);
+    }
+    __device__ __forceinline__ void store(T *row, unsigned v) const
+    {
+        // quad_perm broadcasts of the quad's lanes 1, 2 and 3 (the first lane's own element is v)
+        const unsigned v1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x55, 0xF, 0xF, false);
+        const unsigned v2 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xAA, 0xF, 0xF, false);
+        const unsigned v3 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xFF, 0xF, 0xF, false);
+        store_outputs<T, PK>(row, sc, fwd, kq, n, v, v1, v2, v3);
+    }
+};
+
+//   PairStore (2-byte elements, one channel): lane pairs exchange their 16 bits and the even lane stores both (4 bytes); the pair
+//   (lane, lane + 1) is adjacent in memory forwards and backwards
+struct PairStore {
+    typedef unsigned int word __attribute__((aligned(2)));      // two 2-byte elements, element-aligned
+    int64_t o;              // the pair's first element in memory, relative to the dst row
+    bool head, paired, fwd;
+    __device__ __forceinline__ PairStore(const AxisLaunch &, int k0, int k1, int lane, bool fwd_) : fwd(fwd_)
+    {
+        head = k0 + lane < k1 && !(lane & 1);
+        paired = k0 + lane + 1 < k1;
+        o = fwd ? (int64_t)(k0 + lane) : -(int64_t)(k0 + lane) - (paired ? 1 : 0);
+    }
+    __device__ __forceinline__ void store(unsigned short *row, unsigned v) const
+    {
+        const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);      // quad_perm [1, 0, 3, 2]: the pair's other lane
+        if (head) {
+            if (paired) *reinterpret_cast<word *>(row + o) = fwd ? (v | (other << 16)) : (other | (v << 16));
+            else row[o] = (unsigned short)v;
+        }
+    }
+};
+
+template <int E, bool NT, bool CH, bool PK>
+__global__ __launch_bounds__(kWaves * 64) void aai_axis_narrow_kernel(AxisLaunch a, const AxisEntry *__restrict__ laneTab,
+                                                                       const AxisEntry *__restrict__ rowTab, const AxisStrip *__restrict__ strips,
+                                                                       const typename Elem<E>::T *__restrict__ src, ImageView sv,
+                                                                       typename Elem<E>::T *__restrict__ dst, ImageView dv, int rowsPerBlock)
+{
+    typedef typename Elem<E>::T T;
+    __shared__ __attribute__((aligned(16))) float lds[kWaves][64 * VEC + 8];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int strip = (int)blockIdx.x * kWaves + wave;
+    if (strip >= a.nStrips) return;   // waves are independent: no barrier is skipped by leaving early
+
+    typedef int i4s __attribute__((ext_vector_type(4)));
+    const i4s stq = reinterpret_cast<const i4s *>(strips)[strip];
+    const int k0 = stq.x, k1 = stq.y, x0 = stq.z;
+    const T *img = src + (int64_t)blockIdx.z * sv.imageStride;
+    T *out = dst + (int64_t)blockIdx.z * dv.imageStride + a.outBase;
+    float *line = lds[wave];
+    const int col = x0 + VEC * lane;
+    const int colc = min(col, a.srcW - VEC);        // srcW >= VEC (the route's predicate)
+    const int shift = col - colc;
+
+    const int rowStart = (int)blockIdx.y * rowsPerBlock;
+    const int rowEnd = min(rowStart + rowsPerBlock, a.nB);
+    const int nOut = k1 - k0;
+    const int step = CH ? a.tapStep : 1;
+    const bool fwd = a.outStrideA == 1;              // PK: the lane order is the dst element order (fwd) or its reverse (one channel at 180 degrees)
+
+    if (nOut <= 64) {
+        const bool live = lane < nOut;
+        const Win c = lane_win<CH>(laneTab, live ? k0 + lane : k0, step);
+        const typename Elem<E>::template SmallStore<PK> st(a, k0, k1, lane, fwd);
+        for (int kb = rowStart; kb < rowEnd; ++kb) {
+            const Win e = load_win(rowTab, kb);
+            unsigned v = 0u;
+            if (!half_entry_empty(e.wF, e.wM, e.wL)) {      // (wave-uniform) a dst row off the image reads nothing
+                const Cols s = vertical_pass<E, NT>(img, sv.rowStride, colc, e);
+                __builtin_amdgcn_wave_barrier();
+                park(line, lane, shift, s);
+                __builtin_amdgcn_wave_barrier();
+                v = element<E, CH>(line, c, x0, step);
+            }
+            st.store(out + (int64_t)kb * a.outStrideB, v);
+        }
+    } else {
+        const int kq = k0 + 4 * lane;
+        const int n = min(max(k1 - kq, 0), 4);                   // how many of this lane's four outputs exist
+        const Win c0 = lane_win<CH>(laneTab, n > 0 ? kq : k0, step), c1 = lane_win<CH>(laneTab, n > 1 ? kq + 1 : k0, step);
+        const Win c2 = lane_win<CH>(laneTab, n > 2 ? kq + 2 : k0, step), c3 = lane_win<CH>(laneTab, n > 3 ? kq + 3 : k0, step);
+        const Scatter sc = PK ? Scatter{} : make_scatter(a, kq);
+        for (int kb = rowStart; kb < rowEnd; ++kb) {
+            const Win e = load_win(rowTab, kb);
+            unsigned v0 = 0u, v1 = 0u, v2 = 0u, v3 = 0u;
+            if (!half_entry_empty(e.wF, e.wM, e.wL)) {
+                const Cols s = vertical_pass<E, NT>(img, sv.rowStride, colc, e);
+                __builtin_amdgcn_wave_barrier();
+                park(line, lane, shift, s);
+                __builtin_amdgcn_wave_barrier();
+                v0 = element<E, CH>(line, c0, x0, step);
+                v1 = element<E, CH>(line, c1, x0, step);
+                v2 = element<E, CH>(line, c2, x0, step);
+                v3 = element<E, CH>(line, c3, x0, step);
+            }
+            store_outputs<T, PK>(out + (int64_t)kb * a.outStrideB, sc, fwd, kq, n, v0, v1, v2, v3);
+        }
+    }
+}
+
+// ---- the forwarding route's conversions: lane = four consecutive elements of a row (W elements: pixels x channels), one 4- / 8-byte
+// access on the element side and one 16-byte access on the fp32 side (element-aligned both: rows of any width and pitch); the last
+// elements of a row one by one.  Padding is not touched.
+template <int E>
+__global__ __launch_bounds__(256) void aai_narrow_widen_kernel(const typename Elem<E>::T *__restrict__ src, ImageView sv, float *__restrict__ dst, int W, int H)
+{
+    typedef typename Elem<E>::T T;
+    const int x = ((int)blockIdx.x * 64 + (int)(threadIdx.x & 63)) * 4;
+    if (x >= W) return;
+    const T *img = src + (int64_t)blockIdx.z * sv.imageStride;
+    float *o = dst + (int64_t)blockIdx.z * ((int64_t)W * H);
+    for (int y = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6); y < H; y += (int)gridDim.y * 4) {
+        const T *p = img + (int64_t)y * sv.rowStride + x;
+        float *q = o + (int64_t)y * W + x;
+        if (x + 4 <= W) {
+            Pack<T> r;
+            r.template load<false>(p);
+            const f4 v = {Elem<E>::to_float(r, 0), Elem<E>::to_float(r, 1), Elem<E>::to_float(r, 2), Elem<E>::to_float(r, 3)};
+            *reinterpret_cast<f4u *>(q) = v;
+        } else {
+            for (int i = 0; x + i < W; ++i) q[i] = Elem<E>::widen(p[i]);
+        }
+    }
+}
+
+template <int E>
+__global__ __launch_bounds__(256) void aai_narrow_store_kernel(const float *__restrict__ src, typename Elem<E>::T *__restrict__ dst, ImageView dv, int W, int H)
+{
+    typedef typename Elem<E>::T T;
+    const int x = ((int)blockIdx.x * 64 + (int)(threadIdx.x & 63)) * 4;
+    if (x >= W) return;
+    const float *img = src + (int64_t)blockIdx.z * ((int64_t)W * H);
+    T *o = dst + (int64_t)blockIdx.z * dv.imageStride;
+    for (int y = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6); y < H; y += (int)gridDim.y * 4) {
+        const float *p = img + (int64_t)y * W + x;
+        T *q = o + (int64_t)y * dv.rowStride + x;
+        if (x + 4 <= W) {
+            const f4 v = *reinterpret_cast<const f4u *>(p);
+            Pack<T>::store(q, Elem<E>::from_float(v.x), Elem<E>::from_float(v.y), Elem<E>::from_float(v.z), Elem<E>::from_float(v.w));
+        } else {
+            for (int i = 0; x + i < W; ++i) q[i] = (T)Elem<E>::from_float(p[i]);
+        }
+    }
+}
+
+dim3 convert_grid(int W, int H, int batch)
+{
+    return dim3((unsigned)((W + 255) / 256), (unsigned)std::min((H + 3) / 4, 65535), (unsigned)batch);
+}
+
+template <int E>
+hipError_t launch_axis_typed(const AxisLaunch &a, const AxisShape &shape, const void *src, ImageView sv, void *dst, ImageView dv, hipStream_t stream)
+{
+    typedef typename Elem<E>::T T;
+    const T *s = static_cast<const T *>(src);
+    T *d = static_cast<T *>(dst);
+    const dim3 grid(shape.gridX, shape.gridY, shape.gridZ), block(kWaves * 64);
+    const int rows = shape.rows;
+#define AAI_NARROW_LAUNCH(NT, CH, PK) hipLaunchKernelGGL((aai_axis_narrow_kernel<E, NT, CH, PK>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, s, sv, d, dv, rows)
+    const bool pk = a.outStrideA == 1 || a.outStrideA == -1;
+    if constexpr (Elem<E>::kChannels) {
+        if (a.tapStep > 1) {
+            // (with channels the packed form is 0 degrees, the scattered one 180 degrees)
+            if (pk) { if (shape.nt) AAI_NARROW_LAUNCH(true, true, true); else AAI_NARROW_LAUNCH(false, true, true); }
+            else { if (shape.nt) AAI_NARROW_LAUNCH(true, true, false); else AAI_NARROW_LAUNCH(false, true, false); }
+            return hipGetLastError();
+        }
+    }
+    if (!pk) return hipErrorInvalidValue;      // (one channel: outStrideA is +-1)
+    if (shape.nt) AAI_NARROW_LAUNCH(true, false, true); else AAI_NARROW_LAUNCH(false, false, true);
+#undef AAI_NARROW_LAUNCH
+    return hipGetLastError();
+}
+
+const char *const kNames[4] = {Elem<NARROW_U8>::kName, Elem<NARROW_U16>::kName, Elem<NARROW_F16>::kName, Elem<NARROW_BF16>::kName};
+
+}  // namespace
+
+bool axis_narrow_can_serve(const AxisLaunch &a, int type)
+{
+    if (!narrow_known(type) || a.wide || a.transposed || a.srcW < VEC || a.maxOutputsPerStrip > 256) return false;
+    if (narrow_is_half(type)) return a.tapStep <= 1 && (a.outStrideA == 1 || a.outStrideA == -1);      // single-channel
+    // Measured (profiles/int_time.txt): with more than 64 outputs in some strip (ratios below 4, 1:1, up-sampling) the kernel is 0.54-0.83 of
+    // the forwarding route's time for both integer types and every channel count, and with 16-bit elements also at 4:1 (0.72-0.83); with
+    // 8-bit elements and at most 64 outputs per strip it is not faster beyond the run's spread (0.80-0.98), so that class forwards.
+    return a.maxOutputsPerStrip > 64 || type == NARROW_U16;
+}
+
+hipError_t launch_axis_narrow(const AxisLaunch &a, int type, const void *src, ImageView sv, void *dst, ImageView dv, int batch, hipStream_t stream,
+                              const char **kernelName)
+{
+    if (!narrow_known(type)) return hipErrorInvalidValue;
+    if (kernelName) *kernelName = kNames[type];
+    if (!axis_narrow_can_serve(a, type)) return hipErrorInvalidValue;
+    // K1's launch rules for a 1- / 2-byte source (axis_launch_shape): nontemporal loads unless output rows share source rows, output rows
+    // per workgroup by the rows of a window and the element size.  The plan's measured shape (tuneRows) is fp32's and is not used.
+    const AxisShapeFacts facts{a.nA, a.nB, a.nStrips, 0, a.maxRowSpan, a.rowsShared, a.maxOutputsPerStrip, 0, narrow_is_half(type) ? 1 : a.tapStep, a.outStrideB, 0, 0,
+                               (int)narrow_elem_size(type), batch};
+    const AxisShape shape = axis_launch_shape(facts);
+    if (shape.kernel == AXIS_RUN_NOTHING) return hipSuccess;
+    if (shape.kernel != AXIS_RUN_STRIP) return hipErrorInvalidValue;
+    switch (type) {
+    case NARROW_U8: return launch_axis_typed<NARROW_U8>(a, shape, src, sv, dst, dv, stream);
+    case NARROW_U16: return launch_axis_typed<NARROW_U16>(a, shape, src, sv, dst, dv, stream);
+    case NARROW_F16: return launch_axis_typed<NARROW_F16>(a, shape, src, sv, dst, dv, stream);
+    default: return launch_axis_typed<NARROW_BF16>(a, shape, src, sv, dst, dv, stream);
+    }
+}
+
+hipError_t launch_narrow_widen(int type, const void *src, ImageView sv, float *dst, int W, int H, int batch, hipStream_t stream)
+{
+    if (W <= 0 || H <= 0 || batch <= 0) return hipSuccess;
+    if (!narrow_is_half(type)) return hipErrorInvalidValue;
+    const unsigned short *s = static_cast<const unsigned short *>(src);
+    if (type == NARROW_F16) hipLaunchKernelGGL((aai_narrow_widen_kernel<NARROW_F16>), convert_grid(W, H, batch), dim3(256), 0, stream, s, sv, dst, W, H);
+    else hipLaunchKernelGGL((aai_narrow_widen_kernel<NARROW_BF16>), convert_grid(W, H, batch), dim3(256), 0, stream, s, sv, dst, W, H);
+    return hipGetLastError();
+}
+
+hipError_t launch_narrow_store(int type, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream)
+{
+    if (W <= 0 || H <= 0 || batch <= 0) return hipSuccess;
+    if (!narrow_known(type)) return hipErrorInvalidValue;
+    const dim3 grid = convert_grid(W, H, batch), block(256);
+    unsigned short *d = static_cast<unsigned short *>(dst);
+    switch (type) {
+    case NARROW_U8: hipLaunchKernelGGL((aai_narrow_store_kernel<NARROW_U8>), grid, block, 0, stream, src, static_cast<unsigned char *>(dst), dv, W, H); break;
+    case NARROW_U16: hipLaunchKernelGGL((aai_narrow_store_kernel<NARROW_U16>), grid, block, 0, stream, src, d, dv, W, H); break;
+    case NARROW_F16: hipLaunchKernelGGL((aai_narrow_store_kernel<NARROW_F16>), grid, block, 0, stream, src, d, dv, W, H); break;
+    default: hipLaunchKernelGGL((aai_narrow_store_kernel<NARROW_BF16>), grid, block, 0, stream, src, d, dv, W, H); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace aai

@@ -5,6 +5,7 @@
 // There is deliberately no CPU implementation here: without a HIP device every compute entry point fails with
 // AAI_ERR_NO_DEVICE.  The CPU oracle under oracle/ is test infrastructure and is never linked or loaded.
 #include "aai_engine.hpp"
+#include "../../include/aai_half.h"
 
 #include <chrono>
 #include <climits>
@@ -882,116 +883,88 @@ int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, con
     return for_each_adjoint_chunk(batch, dGdst, dstImageStride, dGsrc, srcImageStride, imageBytes, device, stream, name, false, launch);
 }
 
-// ---- the half-precision path (include/aai_half.h, aai_half.hip)
-int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride, void *dDst,
-                 int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
+// ---- the narrow-element paths (include/aai_half.h, include/aai_int.h; aai_axis_narrow.hip)
+// `type`: aai::NarrowType.  `srcType` is what enqueue() reads on the forwarding route and what keys the plan: the caller's u8 / u16
+// image itself, or the dense fp32 scratch a half image is widened into.
+static int enqueue_narrow(const aai_request &rq, const Geometry &g, int batch, int channels, int type, const void *dSrc, int64_t srcStride,
+                          int64_t srcImageStride, void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
 {
     if (g.dW == 0 || g.dH == 0 || batch == 0) return AAI_OK;
-    // the forward's plan of a packed single-channel fp32 image: the one the forwarding route's launches use, and aai_prepare(req, 1) builds
+    const bool half = aai::narrow_is_half(type);
+    const int srcType = half ? aai::SRC_F32 : type == aai::NARROW_U8 ? aai::SRC_U8 : aai::SRC_U16;
+    const int64_t rowSrc = (int64_t)g.W * channels, rowDst = (int64_t)g.dW * channels;
+    const size_t nSrc = (size_t)rowSrc * (size_t)g.H, nDst = (size_t)rowDst * (size_t)g.dH;
+    const int64_t inStride = half ? rowSrc : srcStride, inImageStride = half ? (int64_t)nSrc : srcImageStride;      // of enqueue()'s source
+    // the forward's plan under (request, channels): the one the forwarding route's enqueue() takes, and aai_prepare(req, channels) builds
     PlanRef p;
-    const int rc = acquire_plan(rq, g, -1, -1, 1, rot_form(rq, g, 1, aai::SRC_F32, (int64_t)g.W), &p, /*onCallerStream*/ true, stream);
+    const int rc = acquire_plan(rq, g, -1, -1, channels, rot_form(rq, g, channels, srcType, inStride), &p, /*onCallerStream*/ true, stream);
     if (rc != AAI_OK) return rc;
-    const uint16_t *src = static_cast<const uint16_t *>(dSrc);
-    uint16_t *dst = static_cast<uint16_t *>(dDst);
+    const int64_t elem = (int64_t)aai::narrow_elem_size(type);
+    const char *src = static_cast<const char *>(dSrc);
+    char *dst = static_cast<char *>(dDst);
     const aai::ImageView sv{srcStride, srcImageStride}, dv{dstStride, dstImageStride};
     hipError_t e = hipSuccess;
-    if (p->kernel == AAI_KERNEL_AXIS && !p->dense && p->flaggedPixels == 0) {
+    if (p->kernel == AAI_KERNEL_AXIS && !p->dense && p->flaggedPixels == 0 && (half || rq.mode == AAI_MODE_AREA || rq.mode == AAI_MODE_FAST)) {
         // (the tables and the launch block are read-only here: no side stream, no event, hence no lock)
-        const aai::AxisLaunch a = make_axis_launch(*p, 1, dstStride);
-        if (aai::axis_half_can_serve(a)) {
+        const aai::AxisLaunch a = make_axis_launch(*p, channels, dstStride);
+        if (aai::axis_narrow_can_serve(a, type)) {
             const char *name = "";
             for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridZ)
-                e = aai::launch_axis_half(a, halfType, src + (int64_t)b0 * srcImageStride, sv, dst + (int64_t)b0 * dstImageStride, dv,
-                                          std::min(batch - b0, kMaxGridZ), stream, &name);
+                e = aai::launch_axis_narrow(a, type, src + (int64_t)b0 * srcImageStride * elem, sv, dst + (int64_t)b0 * dstImageStride * elem, dv,
+                                            std::min(batch - b0, kMaxGridZ), stream, &name);
             g_lastKernel = name;
             if (e != hipSuccess) return hip_fail(e, name);
             return AAI_OK;
         }
     }
-    // forwarding: widen, the fp32 entry's launches, narrow -- the bits of narrow(fp32 entry(widen(src)))
-    const size_t nSrc = (size_t)g.W * (size_t)g.H, nDst = (size_t)g.dW * (size_t)g.dH;
-    const size_t srcBytes = (nSrc * sizeof(float) + 255) & ~(size_t)255, dstBytes = (nDst * sizeof(float) + 255) & ~(size_t)255;
+    // forwarding: (half: widen,) the fp32 entry's launches into dense fp32 scratch, one conversion -- the bits of
+    // narrow(fp32 entry(widen(src))) and of quantize(fp32 entry(src))
+    const size_t srcBytes = half ? (nSrc * sizeof(float) + 255) & ~(size_t)255 : 0, dstBytes = (nDst * sizeof(float) + 255) & ~(size_t)255;
     const int chunk = chunk_images(batch, srcBytes + dstBytes);
     hipMemPool_t pool = nullptr;
     const int rp = adjoint_scratch_pool(p->device, &pool);
     if (rp != AAI_OK) return rp;
     char *scratch = nullptr;
     AAI_HIP(hipMallocFromPoolAsync((void **)&scratch, (srcBytes + dstBytes) * (size_t)chunk, pool, stream));
-    // (dense fp32 images: all the sources of a chunk, then all its outputs)
+    // (dense fp32 images, image b of a chunk at b * nSrc / b * nDst: all the widened sources of a chunk, then all its outputs)
     float *s32 = reinterpret_cast<float *>(scratch), *d32 = reinterpret_cast<float *>(scratch + srcBytes * (size_t)chunk);
+    const char *const storeName = half ? "aai_half_narrow_kernel" : "aai_int_quantize_kernel";
+    const char *what = storeName;
     int rl = AAI_OK;
-    const char *what = "aai_half_widen_kernel";
     for (int b0 = 0; b0 < batch && e == hipSuccess && rl == AAI_OK; b0 += chunk) {
         const int nb = std::min(batch - b0, chunk);
-        what = "aai_half_widen_kernel";
-        e = aai::launch_half_widen(halfType, src + (int64_t)b0 * srcImageStride, sv, s32, g.W, g.H, nb, stream);
-        if (e != hipSuccess) break;
-        rl = enqueue(rq, g, nb, s32, aai::SRC_F32, g.W, (int64_t)nSrc, d32, g.dW, (int64_t)nDst, stream);
+        const char *in = src + (int64_t)b0 * srcImageStride * elem;
+        if (half) {
+            what = "aai_half_widen_kernel";
+            e = aai::launch_narrow_widen(type, in, sv, s32, (int)rowSrc, g.H, nb, stream);
+            if (e != hipSuccess) break;
+        }
+        rl = enqueue(rq, g, nb, half ? (const void *)s32 : in, srcType, inStride, inImageStride, d32, rowDst, (int64_t)nDst, stream, -1, -1, channels);
         if (rl != AAI_OK) break;
-        what = "aai_half_narrow_kernel";
-        e = aai::launch_half_narrow(halfType, d32, dst + (int64_t)b0 * dstImageStride, dv, g.dW, g.dH, nb, stream);
+        what = storeName;
+        e = aai::launch_narrow_store(type, d32, dst + (int64_t)b0 * dstImageStride * elem, dv, (int)rowDst, g.dH, nb, stream);
     }
     const std::string lastError = g_lastError;      // (of a failed enqueue(): hipFreeAsync below must not replace it)
     const hipError_t ef = hipFreeAsync(scratch, stream);
     if (rl != AAI_OK) return fail(rl, lastError);
-    g_lastKernel += "+widened";
+    g_lastKernel += half ? "+widened" : "+quantized";
     if (e != hipSuccess) return hip_fail(e, what);
     if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     return AAI_OK;
 }
 
-// ---- the integer path (include/aai_int.h, aai_int.hip)
+int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride, void *dDst,
+                 int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
+{
+    const int type = halfType == AAI_HALF_F16 ? aai::NARROW_F16 : aai::NARROW_BF16;
+    return enqueue_narrow(rq, g, batch, 1, type, dSrc, srcStride, srcImageStride, dDst, dstStride, dstImageStride, stream);
+}
+
 int enqueue_int(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
                 void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
 {
-    if (g.dW == 0 || g.dH == 0 || batch == 0) return AAI_OK;
-    // the forward's plan under (request, channels): the one enqueue() takes for this source, and aai_prepare(req, channels) builds
-    PlanRef p;
-    const int rc = acquire_plan(rq, g, -1, -1, channels, rot_form(rq, g, channels, srcType, srcStride), &p, /*onCallerStream*/ true, stream);
-    if (rc != AAI_OK) return rc;
-    const int64_t elem = (int64_t)aai::src_elem_size(srcType);
-    char *dst = static_cast<char *>(dDst);
-    const aai::ImageView sv{srcStride, srcImageStride}, dv{dstStride, dstImageStride};
-    hipError_t e = hipSuccess;
-    if (p->kernel == AAI_KERNEL_AXIS && !p->dense && p->flaggedPixels == 0 && (rq.mode == AAI_MODE_AREA || rq.mode == AAI_MODE_FAST)) {
-        // (the tables and the launch block are read-only here: no side stream, no event, hence no lock)
-        const aai::AxisLaunch a = make_axis_launch(*p, channels, dstStride);
-        if (aai::axis_int_can_serve(a, srcType)) {
-            const char *name = "";
-            for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridZ)
-                e = aai::launch_axis_int(a, srcType, src_at(dSrc, srcType, (int64_t)b0 * srcImageStride), sv, dst + (int64_t)b0 * dstImageStride * elem, dv,
-                                         std::min(batch - b0, kMaxGridZ), stream, &name);
-            g_lastKernel = name;
-            if (e != hipSuccess) return hip_fail(e, name);
-            return AAI_OK;
-        }
-    }
-    // forwarding: the interleaved entry's launches into dense fp32 scratch, one conversion -- the bits of quantize(fp32 entry(src))
-    const int64_t rowDst = (int64_t)g.dW * channels;
-    const size_t nDst = (size_t)rowDst * (size_t)g.dH;
-    const size_t dstBytes = (nDst * sizeof(float) + 255) & ~(size_t)255;
-    const int chunk = chunk_images(batch, dstBytes);
-    hipMemPool_t pool = nullptr;
-    const int rp = adjoint_scratch_pool(p->device, &pool);
-    if (rp != AAI_OK) return rp;
-    char *scratch = nullptr;
-    AAI_HIP(hipMallocFromPoolAsync((void **)&scratch, dstBytes * (size_t)chunk, pool, stream));
-    float *d32 = reinterpret_cast<float *>(scratch);      // (dense fp32 outputs: image b of a chunk at b * nDst)
-    int rl = AAI_OK;
-    for (int b0 = 0; b0 < batch && e == hipSuccess && rl == AAI_OK; b0 += chunk) {
-        const int nb = std::min(batch - b0, chunk);
-        rl = enqueue(rq, g, nb, src_at(dSrc, srcType, (int64_t)b0 * srcImageStride), srcType, srcStride, srcImageStride, d32, rowDst, (int64_t)nDst, stream, -1, -1,
-                     channels);
-        if (rl != AAI_OK) break;
-        e = aai::launch_int_quantize(srcType, d32, dst + (int64_t)b0 * dstImageStride * elem, dv, (int)rowDst, g.dH, nb, stream);
-    }
-    const std::string lastError = g_lastError;      // (of a failed enqueue(): hipFreeAsync below must not replace it)
-    const hipError_t ef = hipFreeAsync(scratch, stream);
-    if (rl != AAI_OK) return fail(rl, lastError);
-    g_lastKernel += "+quantized";
-    if (e != hipSuccess) return hip_fail(e, "aai_int_quantize_kernel");
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    return AAI_OK;
+    const int type = srcType == aai::SRC_U8 ? aai::NARROW_U8 : aai::NARROW_U16;
+    return enqueue_narrow(rq, g, batch, channels, type, dSrc, srcStride, srcImageStride, dDst, dstStride, dstImageStride, stream);
 }
 
 int require_device()

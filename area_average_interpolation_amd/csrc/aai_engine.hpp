@@ -220,26 +220,21 @@ int enqueue_f64_forward(const aai_request &rq, const Geometry &g, int batch, con
 int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, const double *dGdst, int64_t dstStride, int64_t dstImageStride, double *dGsrc,
                         int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 
-// The half-precision path (include/aai_half.h; the caller has checked the arguments, strides included): fp16 / bf16 images of raw 16-bit
-// elements in, the same type out, single-channel, every mode.  The plan is the forward's own under its single-channel key (built on the
-// caller's stream by the first call, which blocks; aai_prepare(req, 1) builds the same plan).  Two routes, chosen by static facts of the plan:
-//   DIRECT      kernel AXIS, not dense, no listed pixel, the lane axis along dst x (aai::axis_half_can_serve): aai_axis_half_kernel reads the
-//               half image and writes the half image, no scratch, the batch split at kMaxGridZ
-//   FORWARDING  everything else: widen into fp32 scratch, enqueue() -- the code behind aai_resample_batch_device_f32 -- on the scratch, narrow
-//               into the caller's buffer.  Scratch = a dense fp32 source and a dense fp32 output per image in flight, stream-ordered from
-//               the device's pool (for_each_adjoint_chunk's), the batch in chunks of chunk_images().  aai_last_kernel(): "<fp32 name>+widened".
+// The narrow-element paths (the caller has checked the arguments, strides included): the element type in, the same type out, every mode.
+//   enqueue_half   include/aai_half.h: fp16 / bf16 images of raw 16-bit elements (halfType = AAI_HALF_F16 / AAI_HALF_BF16), single-channel
+//   enqueue_int    include/aai_int.h: u8 / u16 images (srcType = SRC_U8 / SRC_U16) of `channels` interleaved channels
+// Both are one body (enqueue_narrow, aai_engine.cpp).  The plan is the forward's own under the key (request, channels) -- the one the
+// forwarding route's enqueue() takes (for a half image: of a packed fp32 source), built on the caller's stream by the first call, which
+// blocks; aai_prepare(req, channels) builds the same plan.  Two routes, chosen by static facts of the plan:
+//   DIRECT      kernel AXIS, not dense, no listed pixel, the lane axis along dst x (aai::axis_narrow_can_serve); integer images also: area
+//               or fast mode, u16 or more than 64 outputs in some strip.  aai_axis_narrow_kernel reads the image and writes the image, no
+//               scratch, the batch split at kMaxGridZ.  aai_last_kernel(): "aai_axis_half_kernel<f16|bf16>", "aai_axis_int_kernel<u8|u16>".
+//   FORWARDING  everything else: (half: widen into fp32 scratch,) enqueue() -- the code behind aai_resample_batch_device_f32, which reads
+//               u8 / u16 itself -- into dense fp32 output scratch, one conversion into the caller's buffer.  Scratch = (half: a dense fp32
+//               source and) a dense fp32 output per image in flight, stream-ordered from the device's pool (for_each_adjoint_chunk's), the
+//               batch in chunks of chunk_images().  aai_last_kernel(): "<fp32 name>+widened" (half), "<fp32 name>+quantized" (integer).
 int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride, void *dDst,
                  int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
-
-// The integer path (include/aai_int.h; the caller has checked the arguments, strides included): u8 / u16 images (srcType = SRC_U8 /
-// SRC_U16) of `channels` interleaved channels in, the same type out, every mode.  The plan is the forward's own under the key
-// (request, channels) -- what enqueue() uses for this source, and aai_prepare(req, channels) builds.  Two routes, chosen by static facts:
-//   DIRECT      kernel AXIS, not dense, no listed pixel, the lane axis along dst x, area or fast mode, u16 or more than 64 outputs in some
-//               strip (aai::axis_int_can_serve):
-//               aai_axis_int_kernel reads the integer image and writes the integer image, no scratch, the batch split at kMaxGridZ
-//   FORWARDING  everything else: enqueue() -- which reads u8 / u16 itself -- into dense fp32 output scratch, aai_int_quantize_kernel into
-//               the caller's buffer.  Scratch = a dense fp32 output per image in flight, stream-ordered from the device's pool, the batch
-//               in chunks of chunk_images().  aai_last_kernel(): "<fp32 name>+quantized".
 int enqueue_int(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
                 void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
 

@@ -1,11 +1,11 @@
-// aai_half_math.hpp -- the arithmetic of the half-precision path (aai_half.hip; include/aai_half.h), shared with the serial CPU replay
+// aai_half_math.hpp -- the arithmetic of the half-precision path (aai_axis_narrow.hip; include/aai_half.h), shared with the serial CPU replay
 // of the test-suite (tests/emulation/half_emulation.cpp): widening of fp16 / bf16 elements, the vertical sum, the horizontal pass and
 // the single rounding to the element type.
 //
 // The contract (include/aai_half.h): every source element is widened exactly to fp32, the forward's own fp32 weights (the K1 tables of
 // aai_plan.cpp) are applied, sums are fp32, and the result is rounded ONCE to the element type, round-to-nearest-even.  Every fused
 // multiply-add is spelt out (half_fma, like qfma of aai_rot_quad.hpp) and the unit is compiled without contraction (Makefile:
-// NOCONTRACT), so that aai_axis_half_kernel and the replay execute the same IEEE operations in the same order and agree bit for bit.
+// NOCONTRACT), so that aai_axis_narrow_kernel and the replay execute the same IEEE operations in the same order and agree bit for bit.
 //
 // The conversions are plain integer C++: they do not depend on a compiler's or a device's half types.  The kernels may use a hardware
 // conversion where it gives the same bits (fp16 -> fp32 is exact in hardware too: v_cvt_f32_f16 with fp16 denormals preserved, the

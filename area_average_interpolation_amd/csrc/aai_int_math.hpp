@@ -1,4 +1,4 @@
-// aai_int_math.hpp -- the arithmetic of the integer path (aai_int.hip; include/aai_int.h), shared with the serial CPU replay of the
+// aai_int_math.hpp -- the arithmetic of the integer path (aai_axis_narrow.hip; include/aai_int.h), shared with the serial CPU replay of the
 // test-suite (tests/emulation/int_emulation.cpp): the vertical sum and the single-channel horizontal pass are aai_half_math.hpp's,
 // unchanged; this header adds the horizontal pass over interleaved channels (taps `step` elements apart) and the single conversion of
 // an fp32 sum to an 8- or 16-bit unsigned element.
@@ -6,7 +6,7 @@
 // The contract (include/aai_int.h): every source element is used as its integer value (exact in fp32: at most 16 bits), the forward's
 // own fp32 weights (the K1 tables of aai_plan.cpp) are applied, sums are fp32, and the result is converted ONCE: rounded to the nearest
 // integer, ties to even, then saturated to the range of the type.  Every fused multiply-add is spelt out (half_fma) and the unit is
-// compiled without contraction (Makefile: NOCONTRACT), so that aai_axis_int_kernel and the replay execute the same IEEE operations in
+// compiled without contraction (Makefile: NOCONTRACT), so that aai_axis_narrow_kernel and the replay execute the same IEEE operations in
 // the same order and agree bit for bit.
 #pragma once
 

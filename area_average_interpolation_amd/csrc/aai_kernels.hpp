@@ -174,29 +174,26 @@ hipError_t launch_f64_forward(const RotLaunch &r, int batch, const double *src, 
 hipError_t launch_f64_adjoint(const RotLaunch &r, int batch, const double *gdst, ImageView dv, double *n, double *gsrc, ImageView sv,
                               hipStream_t stream, const char **kernelName);
 
-// ---- the half-precision path (aai_half.hip; body in aai_half_math.hpp): fp16 / bf16 images, the element type in and out ----
-// halfType: aai::HalfType (aai_half_math.hpp) = AAI_HALF_F16 / AAI_HALF_BF16; images of raw 16-bit elements, strides in elements.
+// ---- the narrow-element paths (aai_axis_narrow.hip; bodies in aai_half_math.hpp and aai_int_math.hpp): the element type in and out ----
+// The element types of include/aai_half.h (fp16 / bf16, single-channel, images of raw 16-bit elements) and include/aai_int.h (u8 / u16,
+// 1..4 interleaved channels).  The public values AAI_HALF_* and AAI_DTYPE_U* collide, so the engine maps them onto this one.  Strides in elements.
+enum NarrowType { NARROW_U8 = 0, NARROW_U16 = 1, NARROW_F16 = 2, NARROW_BF16 = 3 };
+constexpr bool narrow_known(int type) { return type >= NARROW_U8 && type <= NARROW_BF16; }
+constexpr bool narrow_is_half(int type) { return type == NARROW_F16 || type == NARROW_BF16; }
+constexpr size_t narrow_elem_size(int type) { return type == NARROW_U8 ? 1 : 2; }
 // The direct kernel over K1's tables: whether it serves a launch block (static facts of the plan: not wide, the lane axis along dst x,
-// single-channel, at least four source columns) ...
-bool axis_half_can_serve(const AxisLaunch &a);
-// ... and its launch (hipErrorInvalidValue where it does not).  No scratch.  `batch` <= 65535.
-hipError_t launch_axis_half(const AxisLaunch &a, int halfType, const void *src, ImageView sv, void *dst, ImageView dv, int batch, hipStream_t stream,
-                            const char **kernelName);
-// pitched half images <-> dense fp32 images (W x H elements each, image b at b * W * H).  `batch` <= 65535.
-hipError_t launch_half_widen(int halfType, const void *src, ImageView sv, float *dst, int W, int H, int batch, hipStream_t stream);
-hipError_t launch_half_narrow(int halfType, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream);
-
-// ---- the integer path (aai_int.hip; body in aai_int_math.hpp): u8 / u16 images of 1..4 interleaved channels, the element type in and out ----
-// srcType: SRC_U8 or SRC_U16 (aai_rot_serve.hpp) = AAI_DTYPE_U8 / AAI_DTYPE_U16; strides in elements.
-// The direct kernel over K1's tables: whether it serves a launch block (static facts of the plan: not wide, the lane axis along dst x,
-// at most 256 outputs per strip, at least four elements in a source row; 8-bit elements only with more than 64 outputs in some strip:
-// the measured rule of profiles/int_time.txt) ...
-bool axis_int_can_serve(const AxisLaunch &a, int srcType);
-// ... and its launch (hipErrorInvalidValue where it does not).  No scratch.  `batch` <= 65535.
-hipError_t launch_axis_int(const AxisLaunch &a, int srcType, const void *src, ImageView sv, void *dst, ImageView dv, int batch, hipStream_t stream,
-                           const char **kernelName);
-// dense fp32 images (W x H elements each -- W = pixels x channels --, image b at b * W * H) -> pitched integer images: round to nearest
-// even, saturate (int_quantize).  `batch` <= 65535.
-hipError_t launch_int_quantize(int srcType, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream);
+// at most 256 outputs per strip, at least four elements in a source row; the half types single-channel; 8-bit elements only with more
+// than 64 outputs in some strip: the measured rule of profiles/int_time.txt) ...
+bool axis_narrow_can_serve(const AxisLaunch &a, int type);
+// ... and its launch (hipErrorInvalidValue where it does not).  No scratch.  `batch` <= 65535.  *kernelName: what aai_last_kernel()
+// reports, "aai_axis_half_kernel<f16|bf16>" or "aai_axis_int_kernel<u8|u16>".
+hipError_t launch_axis_narrow(const AxisLaunch &a, int type, const void *src, ImageView sv, void *dst, ImageView dv, int batch, hipStream_t stream,
+                              const char **kernelName);
+// pitched half images -> dense fp32 images (W x H elements each, image b at b * W * H); the half types only (enqueue() reads u8 / u16
+// itself).  `batch` <= 65535.
+hipError_t launch_narrow_widen(int type, const void *src, ImageView sv, float *dst, int W, int H, int batch, hipStream_t stream);
+// dense fp32 images (W x H elements each -- W = pixels x channels --, image b at b * W * H) -> pitched element images, the one conversion
+// of the type: half_narrow or int_quantize.  `batch` <= 65535.
+hipError_t launch_narrow_store(int type, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream);
 
 }  // namespace aai

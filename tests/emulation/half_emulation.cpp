@@ -1,46 +1,22 @@
-// TEST INFRASTRUCTURE ONLY -- serial CPU replay of the half-precision kernel (csrc/aai_half.hip: aai_axis_half_kernel).
+// TEST INFRASTRUCTURE ONLY -- serial CPU replay of the narrow-element kernel on fp16 / bf16 images (csrc/aai_axis_narrow.hip:
+// aai_axis_narrow_kernel, reported as aai_axis_half_kernel).
 //
-// Built by tests/half_cases.py with plain g++ (no HIP, no contraction) into tests/_build/libaai_halfemu.so.  It reuses the PRODUCT's
-// host planner (csrc/aai_plan.cpp: the K1 tables and strips the kernel reads) and the PRODUCT's arithmetic (csrc/aai_half_math.hpp) and
-// walks the kernel's work decomposition one strip, one output row and one output after the other: the vertical sums of the strip's
-// columns into a line, then every output of the strip from the line.  Same IEEE operations in the same order as the kernel, hence its
-// bits.  It is not part of the package, is never loaded by it, and is not a fallback for anything.
-#include <vector>
-
+// Built by tests/half_cases.py with plain g++ (no HIP, no contraction) into tests/_build/libaai_halfemu.so.  The replay itself is
+// narrow_replay.hpp's, with one channel and the conversions of csrc/aai_half_math.hpp.  It is not part of the package, is never loaded
+// by it, and is not a fallback for anything.
 #include "../../area_average_interpolation_amd/csrc/aai_plan.cpp"
-#include "../../area_average_interpolation_amd/csrc/aai_half_math.hpp"
+#include "narrow_replay.hpp"
 
 using namespace aai;
 
 template <int HT>
 static void replay(const Geometry &g, const AxisTables &t, const uint16_t *src, uint16_t *dst, float *pre)
 {
-    const AxisOutMap m = axis_out_map(t, 1, g.dW);
-    std::vector<float> line(STRIP_COLS);
-    for (const AxisStrip &st : t.strips)
-        for (int kb = 0; kb < t.nB; ++kb) {
-            const AxisEntry &e = t.row[kb];
-            const bool emptyRow = half_entry_empty(e.wFirst, e.wMid, e.wLast);
-            if (!emptyRow)
-                for (int x = st.x0; x < st.x0 + STRIP_COLS && x < g.W; ++x) {
-                    float acc = 0.f;
-                    for (int y = e.s0; y <= e.s1; ++y)
-                        acc = half_vertical_step(acc, half_row_weight(e.s0, e.s1, e.wFirst, e.wMid, e.wLast, y), half_widen<HT>(src[(size_t)y * g.W + x]));
-                    line[x - st.x0] = acc;
-                }
-            for (int k = st.k0; k < st.k1; ++k) {
-                const AxisEntry &c = t.lane[k];
-                float v = 0.f;
-                if (!emptyRow && !half_entry_empty(c.wFirst, c.wMid, c.wLast)) v = half_horizontal(line.data(), c.s0 - st.x0, c.s1 - c.s0, c.wFirst, c.wMid, c.wLast);
-                const int64_t o = m.outBase + (int64_t)k * m.outStrideA + (int64_t)kb * m.outStrideB;
-                dst[o] = half_narrow<HT>(v);
-                if (pre) pre[o] = v;
-            }
-        }
+    narrow_replay(g, t, 1, src, dst, pre, [](uint16_t h) { return half_widen<HT>(h); }, [](float v) { return half_narrow<HT>(v); });
 }
 
 // facts[0..7] = axis-aligned, wide, transposed, strips, most outputs in a strip, rows share source rows, most source rows of a window,
-// the direct kernel's static predicate (the part of aai::axis_half_can_serve the tables decide)
+// the direct kernel's static predicate (the part of aai::axis_narrow_can_serve the tables decide)
 extern "C" int aai_emu_half_facts(const aai_request *rq, int *facts)
 {
     Geometry g;

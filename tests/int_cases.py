@@ -59,14 +59,14 @@ _emu = None
 
 
 def emu():
-    """tests/emulation/int_emulation.cpp compiled with g++, no contraction"""
+    """tests/emulation/int_emulation.cpp (over narrow_replay.hpp) compiled with g++, no contraction"""
     global _emu
     if _emu is not None:
         return _emu
     from area_average_interpolation_amd import _lib as L
     os.makedirs(BUILD, exist_ok=True)
     so = os.path.join(BUILD, "libaai_intemu.so")
-    srcs = [os.path.join(ROOT, "tests", "emulation", "int_emulation.cpp")] + [os.path.join(CSRC, f) for f in
+    srcs = [os.path.join(ROOT, "tests", "emulation", f) for f in ("int_emulation.cpp", "narrow_replay.hpp")] + [os.path.join(CSRC, f) for f in
             ("aai_int_math.hpp", "aai_half_math.hpp", "aai_plan.cpp", "aai_plan.hpp", "aai_rot_math.hpp", "aai_strict.hpp")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         r = subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, srcs[0]], capture_output=True, text=True)

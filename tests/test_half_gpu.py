@@ -11,7 +11,7 @@ import pytest
 import half_cases as hc
 import stream_order as so
 from guard_layout import GuardedLayout, to_device, to_numpy
-from test_half_host import replay_case
+from test_half_host import TAIL_CASES, replay_case
 
 pytestmark = pytest.mark.gpu
 
@@ -90,15 +90,19 @@ def test_direct_kernel_has_the_replays_bits(gpu, po, case, mode_name, ht, tname)
 
 
 @pytest.mark.parametrize("ht, tname", hc.TYPES, ids=[t[1] for t in hc.TYPES])
-@pytest.mark.parametrize("case", ["b", "c", "e"])
+@pytest.mark.parametrize("case", ["b", "c", "e"] + TAIL_CASES)
 def test_direct_kernel_memory_contract(gpu, po, case, ht, tname):
     """batch 3, odd padded row strides on both sides, gaps between the images, a base address one element past a 256-byte boundary
-    (2-byte aligned and nothing more).  Source padding holds NaN: a read of it would reach the output.  dst padding holds a sentinel."""
+    (2-byte aligned and nothing more).  Source padding holds NaN: a read of it would reach the output.  dst padding holds a sentinel.
+    The tail cases (test_half_host.TAIL_CASES) end the one strip's store in a quad of lanes with 1, 2 or 3 live outputs."""
     import torch
     B = 3
-    W, H = hc.CASES[case][:2]
+    W, H = (hc.CASES[case] if isinstance(case, str) else case)[:2]
     for mode_name in hc.MODES:
         rq = hc.request(gpu, case, mode_name)
+        if not isinstance(case, str):
+            axis, wide, transposed, strips, most, shared, rowspan, direct = hc.facts(rq)
+            assert direct == 1 and strips == 1 and most == W // 4 <= 64, (case, mode_name, strips, most)
         lay = gpu.query(rq)[2]
         dW, dH = lay.dst_width, lay.dst_height
         sstride = W + 3 + (W % 2)                        # odd

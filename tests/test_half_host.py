@@ -1,7 +1,7 @@
 """The half-precision path (include/aai_half.h: fp16 / bf16 images in, the same type out), checks that need no GPU: ABI, argument errors
 call by call against the fp32 entries' recorded answers, the portable rounding helpers against numpy and torch over the fp32 bit
-patterns that matter, and the serial CPU replay of aai_axis_half_kernel (tests/emulation/half_emulation.cpp over csrc/aai_half_math.hpp
-and the planner's tables) against the oracle on the direct-route geometries.
+patterns that matter, and the serial CPU replay of the direct kernel (tests/emulation/half_emulation.cpp over narrow_replay.hpp,
+csrc/aai_half_math.hpp and the planner's tables) against the oracle on the direct-route geometries.
 
 The two bars of the replay:
   before the rounding   the fp32 value against the oracle on the widened source: conftest.TOL relative, with the suite's floor of 1e-3
@@ -211,7 +211,7 @@ def test_rounding_ties_subnormals_overflow_and_non_finite_values():
 @functools.lru_cache(maxsize=None)
 def replay_case(aai, po, case, mode_name, ht):
     """-> (request, source bits, replay bits, replay fp32 values before the rounding, the oracle on the widened source); computed once"""
-    W, H, sr, dr, iso, ang = hc.CASES[case]
+    W, H, sr, dr, iso, ang = hc.CASES[case] if isinstance(case, str) else case
     rq = hc.request(aai, case, mode_name)
     src = hc.source_bits(W, H, ht)
     out, pre = hc.replay(aai, rq, ht, src)
@@ -219,6 +219,27 @@ def replay_case(aai, po, case, mode_name, ht):
     for a in (src, out, pre, gold):
         a.setflags(write=False)
     return rq, src, out, pre, gold
+
+
+# The tails of the store of a strip of at most 64 outputs, where neighbouring lanes exchange their elements and the first of them stores
+# them: W x 8 images at 4:1, grid-aligned, at 0 and 180 degrees -> ONE strip of W / 4 = 5, 6, 7 outputs, so that the last quad of lanes
+# holds 1, 2, 3 live outputs (and the last pair 1, 2, 1), and 2 output rows.  Geometries as in hc.CASES, kept out of it: the integer
+# tests iterate that table too.
+TAIL_CASES = [pytest.param((W, 8, 4, 1, ((W - 1) / 2, 3.5), ang), id="tail%d@%d" % (W // 4, ang)) for W in (20, 24, 28) for ang in (0.0, 180.0)]
+
+
+@pytest.mark.parametrize("case", TAIL_CASES)
+def test_tail_cases_reach_the_small_strip_store(aai, case):
+    """the direct route, one strip of 5, 6 or 7 outputs, two output rows -- asserted so that a tail case cannot silently move to the
+    other horizontal form or to the forwarding route"""
+    W = case[0]
+    for mode_name in hc.MODES:
+        rq = hc.request(aai, case, mode_name)
+        axis, wide, transposed, strips, most, shared, rowspan, direct = hc.facts(rq)
+        assert (axis, wide, transposed, direct) == (1, 0, 0, 1), (case, mode_name)
+        assert strips == 1 and most == W // 4 <= 64 and most % 4 in (1, 2, 3), (case, mode_name, strips, most)
+        lay = aai.query(rq)[2]
+        assert (lay.dst_width, lay.dst_height) == (W // 4, 2), (case, mode_name)
 
 
 # what the table of the issue says a case reaches: (strips, most outputs in a strip, most source rows of a window); None = not pinned
@@ -251,7 +272,7 @@ def test_direct_route_cases_stay_on_the_direct_route(aai, hostemu, case):
 
 @pytest.mark.parametrize("ht, tname", hc.TYPES, ids=[t[1] for t in hc.TYPES])
 @pytest.mark.parametrize("mode_name", hc.MODES)
-@pytest.mark.parametrize("case", sorted(hc.CASES))
+@pytest.mark.parametrize("case", sorted(hc.CASES) + TAIL_CASES)
 def test_cpu_replay_matches_the_oracle(aai, po, case, mode_name, ht, tname):
     rq, src, out, pre, gold = replay_case(aai, po, case, mode_name, ht)
     assert pre.shape == gold.shape and not np.isnan(pre).any()

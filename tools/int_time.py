@@ -5,9 +5,9 @@ One fresh child process per row (a row = a geometry, an element type and a chann
   (a)  aai_resample_int_batch_device: the integer entry (the direct kernel on every row here)
   (b)  what a user does today: aai_resample_interleaved_device into a preallocated fp32 tensor, then torch round().clamp_(0, max).to(dtype)
   (c)  the library's forwarding route for the same request, from its two stages: (c1) aai_resample_interleaved_device into fp32 -- the
-       launches enqueue() makes -- plus (c2) the stream-ordered scratch and aai_int_quantize_kernel.  No request reaches the forwarding
-       route at a direct-route geometry, so (c2) is measured on the BILINEAR request of the same geometry, which forwards and has the same
-       output size: (c2) = integer entry (bilinear) - aai_resample_interleaved_device (bilinear), medians.
+       launches enqueue() makes -- plus (c2) the stream-ordered scratch and the conversion kernel (aai_narrow_store_kernel).  No request
+       reaches the forwarding route at a direct-route geometry, so (c2) is measured on the BILINEAR request of the same geometry,
+       which forwards and has the same output size: (c2) = integer entry (bilinear) - aai_resample_interleaved_device (bilinear), medians.
 3 warm-up launches of each leg, then N (default 24) timed launches of each between device events; per leg the median and the
 10th..90th percentile.  A row KEEPS the direct route where (a) is faster than (c) beyond the recorded spread: p90(a) < (c) built from
 the favourable ends, p10(c1) + p10(int bilinear) - p90(fp32 bilinear).

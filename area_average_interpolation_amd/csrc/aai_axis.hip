@@ -209,7 +209,13 @@ __device__ __forceinline__ float horizontal_pass(const float *line, int off, int
 // (two output rows in flight per wave) bought 2 % at 2+ rows per workgroup and nothing at 1, so the kernel
 // keeps the simple form: 4 source rows (4 KiB per wave) in flight, latency covered by 8 waves per SIMD.
 // CH: interleaved channels (AxisLaunch::tapStep / outChan); false compiles the single-channel kernel unchanged.
-template <bool NT, typename T, bool CH>
+// BANDED: the workgroup takes its strip block and row block from axis_block_order (aai_plan.hpp) instead of blockIdx: an XCD then
+// streams whole source rows, and the 128-byte line two neighbouring strips share is fetched by one L2 instead of two.  Only
+// <true, float, false, true> is instantiated so -- plain fp32, nontemporal loads, windows that share no source row, quadrants 0 and 2
+// (AxisShape::banded, where the measured loss of the transposed quadrants is quoted); plans whose output rows share source rows keep
+// launch order on purpose: vertically adjacent workgroups there read a common source row, and at gridDim.x == 8 launch order already
+// puts them on one XCD.  Every <..., false> instantiation compiles to the code it had without the flag.
+template <bool NT, typename T, bool CH, bool BANDED = false>
 __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, const AxisEntry *__restrict__ laneTab,
                                                                 const AxisEntry *__restrict__ rowTab, const AxisStrip *__restrict__ strips,
                                                                 const T *__restrict__ src, ImageView sv,
@@ -219,7 +225,10 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: strip/row tables load through the scalar cache
-    const int strip = (int)blockIdx.x * kWaves + wave;
+    // the strip block and row block this workgroup serves: its own place in the grid, or (BANDED) axis_block_order's re-reading of it
+    int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    if constexpr (BANDED) axis_block_order(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, gridDim.y, &bx, &by);
+    const int strip = bx * kWaves + wave;
     if (strip >= a.nStrips) return;   // waves are independent: no barrier is skipped by leaving early
 
     typedef int i4s __attribute__((ext_vector_type(4)));
@@ -232,7 +241,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_kernel(AxisLaunch a, con
     const int colc = min(col, a.srcW - VEC);        // srcW >= VEC here (narrower images use the wide kernel)
     const int shift = col - colc;                    // 0 away from the right edge
 
-    const int rowStart = (int)blockIdx.y * rowsPerBlock;
+    const int rowStart = by * rowsPerBlock;
     const int rowEnd = min(rowStart + rowsPerBlock, a.nB);
     const int nOut = st.k1 - st.k0;
     // interleaved channels: taps `step` elements apart, dst element of lane entry ka split into (pixel, channel)
@@ -591,6 +600,12 @@ static hipError_t launch_axis_typed(const AxisLaunch &a, const T *src, ImageView
         if (nt) hipLaunchKernelGGL((aai_axis_kernel<true, T, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);
         else hipLaunchKernelGGL((aai_axis_kernel<false, T, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);
     } else {
+        if constexpr (sizeof(T) == 4) {
+            if (shape.banded) {
+                hipLaunchKernelGGL((aai_axis_kernel<true, T, false, true>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);
+                return hipGetLastError();
+            }
+        }
         if (nt) hipLaunchKernelGGL((aai_axis_kernel<true, T, false>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);
         else hipLaunchKernelGGL((aai_axis_kernel<false, T, false>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, src, sv, dst, dv, rows);
     }

@@ -206,7 +206,7 @@ static aai::AxisLaunch make_axis_launch(const Plan &p, int channels, int64_t dst
 // the class (same device, same rows per footprint, same row sharing, same width class) take the result from a cache.
 // Bounds: plain fp32 images, footprints of >= 4 source rows, un-transposed quadrants, whole image; scratch of at most
 // ~1.25 GiB of source copies plus their outputs (images too large for that take the class's cached shape or the built-in
-// one); a private stream; about 10 ms.  AAI_AXIS_AUTOTUNE=0 disables it.  (Documented in include/aai.h at aai_prepare.)
+// one); a private stream; about 13 ms (profiles/axis_order.txt).  AAI_AXIS_AUTOTUNE=0 disables it.  (Documented in include/aai.h at aai_prepare.)
 struct TuneKey {
     int device, rowSpan, rowsShared, widthClass;
     bool operator<(const TuneKey &o) const
@@ -256,26 +256,58 @@ static void tune_axis_plan(Plan &p, int channels, int band0, hipStream_t stream)
     struct Shape { int rows, nt; float ms; };
     Shape shapes[] = {{1, 1, 0.f}, {2, 1, 0.f}, {1, 0, 0.f}, {2, 0, 0.f}, {4, 1, 0.f}};
     const aai::ImageView sv{g.W, (int64_t)g.W * g.H}, dv{g.dW, (int64_t)g.dW * g.dH};
-    // the shapes take turns, two rounds after a warm-up round, two launches per turn; each keeps its faster turn
+    static const bool trace = [] { const char *v = getenv("AAI_TRACE_PLAN"); return v && atoi(v) != 0; }();
+    // one timed turn of a shape: `launches` launches between two events
+    auto turn = [&](const Shape &sh, int launches, float &ms) {
+        p.tuneRows = sh.rows; p.tuneNt = sh.nt;
+        const aai::AxisLaunch a = make_axis_launch(p, 1, g.dW);
+        ms = 0.f;
+        bool good = hipEventRecord(e0, stream) == hipSuccess;
+        for (int i = 0; i < launches && good; ++i) good = aai::launch_axis(a, src, aai::SRC_F32, sv, dst, dv, images, stream, nullptr) == hipSuccess;
+        return good && hipEventRecord(e1, stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+    };
+    // the shapes take turns, two rounds after a warm-up round, two launches per turn; each keeps its faster turn.  This only RANKS
+    // them: two turns right after allocation are too thin to decide between shapes a few per cent apart
     for (int round = 0; round < 3 && ok; ++round)
         for (Shape &sh : shapes) {
-            p.tuneRows = sh.rows; p.tuneNt = sh.nt;
-            const aai::AxisLaunch a = make_axis_launch(p, 1, g.dW);
             float ms = 0.f;
-            ok = ok && hipEventRecord(e0, stream) == hipSuccess &&
-                 aai::launch_axis(a, src, aai::SRC_F32, sv, dst, dv, images, stream, nullptr) == hipSuccess &&
-                 aai::launch_axis(a, src, aai::SRC_F32, sv, dst, dv, images, stream, nullptr) == hipSuccess &&
-                 hipEventRecord(e1, stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+            ok = ok && turn(sh, 2, ms);
             if (ok && round > 0 && (sh.ms == 0.f || ms < sh.ms)) sh.ms = ms;       // round 0 warms up
+            if (ok && trace) fprintf(stderr, "[aai tune] round %d rows=%d nt=%d  %.4f ms per launch\n", round, sh.rows, sh.nt, ms / 2);
         }
+    // The decision is a duel of the two fastest: kDuelTurns alternating turns of kDuelLaunches launches each, medians compared.  The
+    // shapes that ever win lie 4 to 8 % apart and the turns of one shape lie within 1 to 4 % of their median (profiles/axis_order.txt), so
+    // the medians of 12 turns settle a difference of 2 % in every process.  The earlier of the two in the list (the built-in shape
+    // comes first) is kept unless the other's median is lower by more than 1 %.
+    constexpr int kDuelTurns = 12, kDuelLaunches = 4;
+    const Shape *first = nullptr, *second = nullptr;
+    if (ok) {
+        for (const Shape &sh : shapes)
+            if (!first || sh.ms < first->ms) { second = first; first = &sh; }
+            else if (!second || sh.ms < second->ms) second = &sh;
+        if (second < first) std::swap(first, second);                       // list order: `first` is the incumbent
+        float t[2][kDuelTurns];
+        for (int i = 0; i < kDuelTurns && ok; ++i)
+            for (int s = 0; s < 2 && ok; ++s) ok = turn(s ? *second : *first, kDuelLaunches, t[s][i]);
+        if (ok) {
+            for (int s = 0; s < 2; ++s) std::sort(t[s], t[s] + kDuelTurns);
+            const float m0 = 0.5f * (t[0][kDuelTurns / 2 - 1] + t[0][kDuelTurns / 2]), m1 = 0.5f * (t[1][kDuelTurns / 2 - 1] + t[1][kDuelTurns / 2]);
+            if (trace)
+                for (int s = 0; s < 2; ++s) {
+                    const Shape &sh = s ? *second : *first;
+                    fprintf(stderr, "[aai tune] duel rows=%d nt=%d  median %.4f ms per launch, turns", sh.rows, sh.nt, (s ? m1 : m0) / kDuelLaunches);
+                    for (int i = 0; i < kDuelTurns; ++i) fprintf(stderr, " %.4f", t[s][i] / kDuelLaunches);
+                    fprintf(stderr, "\n");
+                }
+            if (m1 < m0 * 0.99f) first = second;
+            if (trace) fprintf(stderr, "[aai tune] chosen rows=%d nt=%d\n", first->rows, first->nt);
+        }
+    }
     p.tuneRows = 0; p.tuneNt = 0;
     if (ok) {
-        const Shape *best = &shapes[0];
-        for (const Shape &sh : shapes)
-            if (sh.ms < best->ms * 0.99f) best = &sh;          // a later shape must win by more than the timing noise
-        p.tuneRows = best->rows; p.tuneNt = best->nt; p.tuneSource = 1;
+        p.tuneRows = first->rows; p.tuneNt = first->nt; p.tuneSource = 1;
         std::lock_guard<std::mutex> lock(g_tuneMutex);
-        tune_cache()[key] = TuneShape{best->rows, best->nt};
+        tune_cache()[key] = TuneShape{first->rows, first->nt};
     }
     (void)hipGetLastError();
     if (e0) (void)hipEventDestroy(e0);
@@ -492,8 +524,15 @@ std::string plan_description(const aai_request &rq, int channels)
         if (p.device == dev && p.band0 < 0 && (rotated || p.channels == channels) && p.built && same_request(p.key, rq)) {
             char buf[320];
             // (swap=0: the grid-order field stays in the format that bench.py, the tests and the recorded profiles read; new tokens go at the end)
-            int len = snprintf(buf, sizeof buf, "kernel=%d rows=%d nt=%d swap=0 tune=%s flagged=%u dense=%d form=%s build_ms=%.3f adjoint=%s rot_adjoint=%s", p.kernel, p.tuneRows, p.tuneNt,
-                     p.tuneSource == 1 ? "measured" : (p.tuneSource == 2 ? "cached" : "default"), p.flaggedPixels, p.dense ? 1 : 0,
+            // order: the workgroup order K1 runs a plain fp32 image of this plan in (AxisShape::banded, aai_plan.hpp)
+            bool banded = false;
+            if (p.kernel == AAI_KERNEL_AXIS && p.channels == 1) {
+                const aai::AxisLaunch a = make_axis_launch(p, 1, p.g.dW);
+                banded = aai::axis_launch_shape(aai::AxisShapeFacts{a.nA, a.nB, a.nStrips, a.wide, a.maxRowSpan, a.rowsShared, a.maxOutputsPerStrip, a.transposed, a.tapStep,
+                                                                    a.outStrideB, a.tuneRows, a.tuneNt, 4, 1}).banded != 0;
+            }
+            int len = snprintf(buf, sizeof buf, "kernel=%d rows=%d nt=%d swap=0 tune=%s order=%s flagged=%u dense=%d form=%s build_ms=%.3f adjoint=%s rot_adjoint=%s", p.kernel, p.tuneRows, p.tuneNt,
+                     p.tuneSource == 1 ? "measured" : (p.tuneSource == 2 ? "cached" : "default"), banded ? "banded" : "launch", p.flaggedPixels, p.dense ? 1 : 0,
                      p.kernel == AAI_KERNEL_ROTATED ? (p.form == aai::ROT_FORM_CELL ? "cell" : "quad") : "-", p.buildMs, p.adjState == 1 ? "tables" : "none",
                      p.rotAdjState == 1 ? "sums" : (p.rotAdjState == 2 ? "general" : "none"));
             if (p.adjKnife >= 0 && len > 0 && len < (int)sizeof buf) snprintf(buf + len, sizeof buf - (size_t)len, " knife=%lld", p.adjKnife);

@@ -139,7 +139,7 @@ int require_device();
 // stream that is being captured into a graph is not used), else on the device pool's build stream).
 // form: aai::RotForm of a rotated request's launch (rot_form below); ignored by the other kernels
 int acquire_plan(const aai_request &rq, const Geometry &g, int band0, int band1, int channels, int form, PlanRef *out, bool onCallerStream = false, hipStream_t stream = nullptr);
-// "kernel=K rows=R nt=N swap=0 tune=T flagged=F dense=D form=M build_ms=B adjoint=tables|none rot_adjoint=none|sums|general[ knife=N]" of the
+// "kernel=K rows=R nt=N swap=0 tune=T order=banded|launch flagged=F dense=D form=M build_ms=B adjoint=tables|none rot_adjoint=none|sums|general[ knife=N]" of the
 // cached whole-image plan ("" when there is none); new tokens are appended at the end
 std::string plan_description(const aai_request &rq, int channels);
 // which fp32 formulation serves a launch of this request: the cell formulation takes plain images below 4 GiB in area mode

@@ -183,7 +183,30 @@ struct AxisShape {
     int rows;                    // output rows per workgroup (strip kernel; the tile kernel's workgroups take kAxisWaves * kAxisTileCols)
     int tileNR;                  // tile kernel: source rows per pipeline window (axis_tile_window_rows)
     unsigned gridX, gridY, gridZ;      // strip and tile kernels (the wide kernel: gridX and gridZ; its rows go in launches of 65535 * 4)
+    int banded;                  // strip kernel: workgroups take their (strip block, row block) from axis_block_order
 };
+
+// The banded workgroup order of the strip kernel's streaming class.  Workgroups are dealt round-robin over the 8 XCDs, each with an L2
+// of its own, and every 4 KiB piece a strip reads shares its first 128-byte line with the strip to its left.  In launch order the
+// strip blocks of one row block are CONSECUTIVE workgroups and so sit behind eight different L2s (at gridX == 8, XCD j reads column
+// block j of every row and nothing else): every shared line is fetched twice.  Here the linear index b = blockIdx.y * gridX +
+// blockIdx.x of a workgroup within its image is re-read: of every group of 8 gridX consecutive workgroups, those with equal b % 8
+// take ONE whole row block, strip block by strip block (xcd_tile's arithmetic, aai_quad_src.hpp, with a band of one row block), so
+// that the eight XCDs advance in step over eight consecutive row blocks.  The row blocks past the last whole group of 8 keep launch
+// order: the grid stays exactly axis_launch_shape's, the map is a bijection of [0, gridX gridY) for every grid, and nothing depends
+// on where a workgroup really runs -- a different placement costs the shared lines again, never a result.
+AAI_HD void axis_block_order(unsigned b, unsigned gridX, unsigned gridY, int *bx, int *by)
+{
+    const unsigned group = 8u * gridX, banded = (gridY >> 3) * group;      // workgroups of the whole groups of 8 row blocks
+    if (b >= banded) {
+        *bx = (int)(b % gridX);
+        *by = (int)(b / gridX);
+        return;
+    }
+    const unsigned super = b / group, within = b - super * group;
+    *bx = (int)(within >> 3);
+    *by = (int)(super * 8u + (within & 7u));
+}
 
 // The tile kernel's pipeline: windows of at most four source rows (ratios up to 3) run eight output rows in flight, windows of up to
 // eight rows (ratios up to 4, where a strip still holds more than 64 outputs) four.  Asked by aai_axis_tile_kernel itself.
@@ -243,6 +266,13 @@ inline AxisShape axis_launch_shape(const AxisShapeFacts &a)
     // the plan's measured choice for this (geometry, device) -- fp32 sources only (aai_engine.cpp: tune_axis_plan)
     if (a.elemBytes == 4 && a.tuneRows > 0) { rows = a.tuneRows; nt = a.tuneNt; }
     s.nt = nt;
+    // the banded order (axis_block_order): plain fp32 sources whose windows share no source row, streamed with nontemporal loads.
+    // Plans with shared rows keep launch order on purpose: vertically adjacent workgroups there read a common source row, and at
+    // gridX == 8 launch order already puts them on one XCD.  The transposed quadrants keep launch order too: consecutive row blocks
+    // there write neighbouring dst COLUMNS, i.e. the same dst lines, and launch order keeps those behind one L2 -- banded, 8192^2 at 90
+    // degrees went from 53.8 to 60.5 us at 4:1 (270 degrees: 53.1 to 60.7) and from 47.6 to 54.2 us at 8:1, where 0 / 180 degrees gain
+    // (48.9 to 46.6, 47.7 to 46.6; 16:1 46.3 to 44.5; profiles/axis_order.txt).  (Set for the strip kernel only, below.)
+    const int banded = nt && !a.rowsShared && !a.transposed && a.elemBytes == 4 && a.tapStep <= 1;
     // The LDS-tile kernel (measured, profiles/r01_axis_transposed.txt: wins below 2:1 -- 1:1 1.8 -> 2.3 TB/s, x4 up-sampling 1.2 -> 1.6 --
     // and loses 5-14 % to the four-column register path between 2:1 and 4:1)
     // ... and, since its output rows run in a software pipeline and its waves store together, down to 64 outputs per strip (ratios up
@@ -265,6 +295,7 @@ inline AxisShape axis_launch_shape(const AxisShapeFacts &a)
     s.rows = rows;
     s.gridX = (unsigned)((a.nStrips + kAxisWaves - 1) / kAxisWaves);
     s.gridY = (unsigned)blocksY;
+    s.banded = banded;
     return s;
 }
 

@@ -191,7 +191,8 @@ int aai_prepare(const aai_request *req, int32_t channels /* 1 for plain images; 
  *     one scan kernel over the output; and, for the FIRST large plain-fp32 geometry of a class (same device, same source
  *     rows per output row, same width class) measures which launch shape streams fastest on this device: transient
  *     scratch of 2..8 source-sized images (at most 1.25 GiB; larger sources skip the measurement) plus their outputs,
- *     ~40 launches on a private stream, ~10 ms.  Later plans of the class reuse the result.  AAI_AXIS_AUTOTUNE=0 in the
+ *     ~130 launches on a private stream (every candidate shape in turn, then a duel of alternating turns between the two fastest,
+ *     decided by their medians), ~13 ms.  Later plans of the class reuse the result.  AAI_AXIS_AUTOTUNE=0 in the
  *     environment disables the measurement (built-in shape).
  *   - rotated area / fast requests: one or two scan kernels over the output (pixels left to the double-precision pass).
  * All of it runs on a private stream and blocks only the calling thread: plans of other requests, devices and threads are
@@ -205,7 +206,7 @@ int aai_prepare(const aai_request *req, int32_t channels /* 1 for plain images; 
  *   AAI_TRACE_PLAN=1         stage timings of every plan build on stderr
  *
  * aai_plan_info writes a one-line description of the cached whole-image plan of `req` on the current device into `text`
- * ("" when there is none yet): "kernel=K rows=R nt=N swap=0 tune=measured|cached|default flagged=F dense=D form=cell|quad|-
+ * ("" when there is none yet): "kernel=K rows=R nt=N swap=0 tune=measured|cached|default order=banded|launch flagged=F dense=D form=cell|quad|-
  * build_ms=B adjoint=tables|none" -- the kernel family (AAI_KERNEL_*), K1's launch shape (swap is always 0) and where it came from,
  * the dst pixels the double-precision pass owns, the fp32 formulation of a rotated area request, what building the plan cost, and
  * whether the plan holds the tables of the planned adjoint (aai_adjoint_prepare; new tokens are appended at the end of the line). */

@@ -154,6 +154,13 @@ INT_SYMBOLS = {
     "aai_resample_int_host": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
 }
 
+# the extension header include/aai_half_interleaved.h: fp16 / bf16 images of 1..4 interleaved channels in and out (the argument lists of
+# include/aai_int.h's entries, the half element type in the place of the integer one)
+HALF_INTERLEAVED_SYMBOLS = {
+    "aai_resample_half_interleaved_device": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_resample_half_interleaved_host": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
+}
+
 _lib = None
 
 
@@ -177,7 +184,7 @@ def load():
         for name, (res, args) in (list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()) + list(INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(ROTATED_ADJOINT_SYMBOLS.items()) + list(ROTATED_INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items()) + list(SAMPLE_ADJOINT_SYMBOLS.items()) + list(F64_SYMBOLS.items()) +
-                                  list(HALF_SYMBOLS.items()) + list(INT_SYMBOLS.items())):
+                                  list(HALF_SYMBOLS.items()) + list(INT_SYMBOLS.items()) + list(HALF_INTERLEAVED_SYMBOLS.items())):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

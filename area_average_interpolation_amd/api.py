@@ -562,6 +562,54 @@ def resample_half_host(src, src_resolution, dst_resolution, src_isocenter, rotat
     return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
 
 
+def resample_half_interleaved_device(request, channels, src_ptr, src_stride, dst_ptr, dst_stride, half_dtype, stream=0, batch=None, src_image_stride=0,
+                                     dst_image_stride=0):
+    """aai_resample_half_interleaved_device (include/aai_half_interleaved.h): resample_half_device for images of `channels` = 1..4
+    interleaved channels -- element (x, y, c) at y * stride + x * channels + c, resample_interleaved_device's layout, which is a
+    channels-last tensor's -- read and written in place in the element type.  Raw device pointers (ints), strides in 2-byte elements, a
+    hipStream_t handle.  The plan is resample_interleaved_device's (prepare(request, channels) prepares this call too); rotations by
+    0 / 180 degrees in the area / fast modes run one streaming kernel (last_kernel(): "aai_axis_half_kernel<f16>" / "<bf16>"),
+    everything else widens into fp32 scratch, runs resample_interleaved_device's launches and narrows ("<fp32 kernel>+widened")."""
+    rc = L.load().aai_resample_half_interleaved_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(half_dtype), src_ptr, src_stride,
+                                                       src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def resample_half_interleaved_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
+                                   half_dtype=None):
+    """Host-buffer half-precision interleaved forward (aai_resample_half_interleaved_host): src is a [H, W, C] (C = 1..4, interleaved) or
+    [H, W] image of np.float16 (half_dtype HALF_F16, the default for that dtype) or of np.uint16 holding raw bfloat16 bits (HALF_BF16,
+    the default for that dtype); the result has src's dtype and [dH, dW, C] or [dH, dW] shape.  The bits of
+    resample_half_interleaved_device.
+
+    Returns (code, message, dst ndarray or None, (dstIsoX, dstIsoY) or None, Layout or None)."""
+    lib = L.load()
+    a = np.asarray(src)
+    if a.dtype not in (np.float16, np.uint16):
+        raise TypeError("resample_half_interleaved_host takes np.float16 (fp16) or np.uint16 (raw bf16 bits) images, got %s" % a.dtype)
+    if half_dtype is None:
+        half_dtype = L.HALF_F16 if a.dtype == np.float16 else L.HALF_BF16
+    if a.ndim not in (2, 3):
+        if a.size != 0:
+            raise ValueError("src must be an image [H, W] or [H, W, C]")
+        a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
+    a = np.ascontiguousarray(a)
+    H, W = a.shape[:2]
+    C = a.shape[2] if a.ndim == 3 else 1
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None, None, None
+    dst = np.empty((lay.dst_height, lay.dst_width) + ((C,) if a.ndim == 3 else ()), dtype=a.dtype)
+    out_lay = L.Layout()
+    rc = lib.aai_resample_half_interleaved_host(_ref(rq), C, int(half_dtype), a.ctypes.data, max(W * C, 1), dst.ctypes.data, max(lay.dst_width * C, 1),
+                                                ctypes.byref(out_lay))
+    if rc != L.OK:
+        return rc, last_error(), None, None, None
+    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+
+
 def resample_int_device(request, channels, src_ptr, src_stride, dst_ptr, dst_stride, dtype, stream=0, batch=None, src_image_stride=0, dst_image_stride=0):
     """aai_resample_int_batch_device (include/aai_int.h): the forward on device-resident 8-bit (dtype = DTYPE_U8) or 16-bit (DTYPE_U16)
     unsigned images of `channels` = 1..4 interleaved channels, which writes the SAME element type: every source element as its integer

@@ -1,5 +1,5 @@
 // aai_axis_narrow.hip -- the narrow-element paths: images whose elements are narrower than fp32 in, the same element type out.
-//   include/aai_half.h   fp16 / bf16, single-channel
+//   include/aai_half.h   fp16 / bf16, single-channel  (include/aai_half_interleaved.h: 1..4 interleaved channels)
 //   include/aai_int.h    u8 / u16, 1..4 interleaved channels
 //
 //   aai_axis_narrow_kernel<E>   the DIRECT route: K1's streaming form (aai_axis.hip) over the forward plan's cached tables -- strips, lane
@@ -17,7 +17,7 @@
 // elements apart (CH; the single-channel form is compiled without the step).  Waves never synchronise with each other: no workgroup barrier.
 // Two forms of the horizontal pass, chosen per strip (wave-uniform) like K1's branches C and D:
 //   * up to 64 outputs in the strip (ratios of 4 and more): one output per lane; neighbouring lanes exchange their elements through
-//     DPP and the first of them stores them (the type's SmallStore: the four lanes of a quad, or a pair of lanes);
+//     DPP and the first of them stores them (the type's SmallStore: the four lanes of a quad, or -- half types, one channel -- a pair);
 //   * 65 .. 256 outputs (ratios below 4, 1:1, up-sampling -- a strip never holds more than 256, build_axis_strips): four consecutive
 //     outputs per lane.
 // Stores: where the lane order is the dst element order -- 0 degrees with any channel count (forwards), 180 degrees with one channel
@@ -28,9 +28,13 @@
 // What an element type decides (Elem<E>), and nothing else:
 //   u8     v_cvt_f32_ubyte<i> in; round to nearest even, saturate (int_quantize) out; 4-byte packs; channels; quad store
 //   u16    shift / mask and convert in; int_quantize out; 8-byte packs; channels; quad store
-//   f16    v_cvt_f32_f16 in (exact); v_cvt_f16_f32 with the canonical NaN of aai_half_math.hpp out; u16's packs; one channel; pair store
-//   bf16   shift / mask in (the bits ARE the fp32's upper half); f32_to_bf16 out; u16's packs; one channel; pair store
-// (The pair store is measured, profiles/narrow_time.txt: with the quad store the half 4:1 rows took about 0.5-1 us more of 107-117 us.)
+//   f16    v_cvt_f32_f16 in (exact); v_cvt_f16_f32 with the canonical NaN of aai_half_math.hpp out; u16's packs; channels; pair store
+//          with one channel, quad store with more
+//   bf16   shift / mask in (the bits ARE the fp32's upper half); f32_to_bf16 out; u16's packs; channels; pair / quad store like f16
+// (The pair store is measured, profiles/narrow_time.txt: with the quad store the half 4:1 rows took about 0.5-1 us more of 107-117 us.
+// It pairs lanes that are adjacent in memory forwards and backwards, which holds for one channel only: at 180 degrees the pixels of an
+// interleaved row run backwards and the channels of a pixel forwards, so with channels the half types take the quad store, whose
+// scattered form places every element by itself.)
 //
 // The arithmetic of an element is aai_half_math.hpp's and aai_int_math.hpp's, operation for operation, and this unit is compiled
 // without contraction: the CPU replays of the tests (tests/emulation/narrow_replay.hpp behind half_emulation.cpp and int_emulation.cpp)
@@ -42,6 +46,7 @@
 #include "aai_int_math.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace aai {
 
@@ -91,24 +96,22 @@ template <> struct Pack<unsigned short> {
 template <typename T, bool PK> struct QuadStore;
 struct PairStore;
 
-// The element policy: storage type, element i of a pack as a float, a float as an element (in the low bits), whether the type has
-// interleaved-channel forms, the store of a strip of at most 64 outputs, the name aai_last_kernel() reports.
+// The element policy: storage type, element i of a pack as a float, a float as an element (in the low bits), the store of a strip of
+// at most 64 outputs as a function of the kernel's form (CH, PK), the name aai_last_kernel() reports.
 template <int E> struct Elem;
 
 template <> struct Elem<NARROW_U8> {
     typedef unsigned char T;
-    static constexpr bool kChannels = true;
     static constexpr const char *kName = "aai_axis_int_kernel<u8>";
-    template <bool PK> using SmallStore = QuadStore<T, PK>;
+    template <bool CH, bool PK> using SmallStore = QuadStore<T, PK>;
     static __device__ __forceinline__ float to_float(const Pack<T> &p, int i) { return (float)((p.w >> (8 * i)) & 255u); }     // v_cvt_f32_ubyte<i>
     static __device__ __forceinline__ unsigned from_float(float f) { return (unsigned)int_quantize<T>(f); }
 };
 
 template <> struct Elem<NARROW_U16> {
     typedef unsigned short T;
-    static constexpr bool kChannels = true;
     static constexpr const char *kName = "aai_axis_int_kernel<u16>";
-    template <bool PK> using SmallStore = QuadStore<T, PK>;
+    template <bool CH, bool PK> using SmallStore = QuadStore<T, PK>;
     static __device__ __forceinline__ float to_float(const Pack<T> &p, int i) { return (float)(((i < 2 ? p.w0 : p.w1) >> (16 * (i & 1))) & 65535u); }
     static __device__ __forceinline__ unsigned from_float(float f) { return (unsigned)int_quantize<T>(f); }
 };
@@ -117,9 +120,8 @@ template <> struct Elem<NARROW_U16> {
 // (round to nearest even, overflow to Inf, subnormals kept) with the header's canonical NaN
 template <> struct Elem<NARROW_F16> {
     typedef unsigned short T;
-    static constexpr bool kChannels = false;
     static constexpr const char *kName = "aai_axis_half_kernel<f16>";
-    template <bool PK> using SmallStore = PairStore;
+    template <bool CH, bool PK> using SmallStore = std::conditional_t<CH, QuadStore<T, PK>, PairStore>;
     static __device__ __forceinline__ float widen(unsigned bits16) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16); }
     static __device__ __forceinline__ float to_float(const Pack<T> &p, int i)
     {
@@ -136,9 +138,8 @@ template <> struct Elem<NARROW_F16> {
 // bf16: the bits of half_widen / half_narrow<HALF_BF16>, the narrowing in the header's integer form
 template <> struct Elem<NARROW_BF16> {
     typedef unsigned short T;
-    static constexpr bool kChannels = false;
     static constexpr const char *kName = "aai_axis_half_kernel<bf16>";
-    template <bool PK> using SmallStore = PairStore;
+    template <bool CH, bool PK> using SmallStore = std::conditional_t<CH, QuadStore<T, PK>, PairStore>;
     static __device__ __forceinline__ float widen(unsigned bits16) { return __uint_as_float(bits16 << 16); }
     static __device__ __forceinline__ float to_float(const Pack<T> &p, int i)
     {
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(kWaves * 64) void aai_axis_narrow_kernel(AxisLaunch
     if (nOut <= 64) {
         const bool live = lane < nOut;
         const Win c = lane_win<CH>(laneTab, live ? k0 + lane : k0, step);
-        const typename Elem<E>::template SmallStore<PK> st(a, k0, k1, lane, fwd);
+        const typename Elem<E>::template SmallStore<CH, PK> st(a, k0, k1, lane, fwd);
         for (int kb = rowStart; kb < rowEnd; ++kb) {
             const Win e = load_win(rowTab, kb);
             unsigned v = 0u;
@@ -444,13 +445,11 @@ hipError_t launch_axis_typed(const AxisLaunch &a, const AxisShape &shape, const 
     const int rows = shape.rows;
 #define AAI_NARROW_LAUNCH(NT, CH, PK) hipLaunchKernelGGL((aai_axis_narrow_kernel<E, NT, CH, PK>), grid, block, 0, stream, a, a.laneTab, a.rowTab, a.strips, s, sv, d, dv, rows)
     const bool pk = a.outStrideA == 1 || a.outStrideA == -1;
-    if constexpr (Elem<E>::kChannels) {
-        if (a.tapStep > 1) {
-            // (with channels the packed form is 0 degrees, the scattered one 180 degrees)
-            if (pk) { if (shape.nt) AAI_NARROW_LAUNCH(true, true, true); else AAI_NARROW_LAUNCH(false, true, true); }
-            else { if (shape.nt) AAI_NARROW_LAUNCH(true, true, false); else AAI_NARROW_LAUNCH(false, true, false); }
-            return hipGetLastError();
-        }
+    if (a.tapStep > 1) {
+        // (with channels the packed form is 0 degrees, the scattered one 180 degrees)
+        if (pk) { if (shape.nt) AAI_NARROW_LAUNCH(true, true, true); else AAI_NARROW_LAUNCH(false, true, true); }
+        else { if (shape.nt) AAI_NARROW_LAUNCH(true, true, false); else AAI_NARROW_LAUNCH(false, true, false); }
+        return hipGetLastError();
     }
     if (!pk) return hipErrorInvalidValue;      // (one channel: outStrideA is +-1)
     if (shape.nt) AAI_NARROW_LAUNCH(true, false, true); else AAI_NARROW_LAUNCH(false, false, true);
@@ -465,7 +464,12 @@ const char *const kNames[4] = {Elem<NARROW_U8>::kName, Elem<NARROW_U16>::kName, 
 bool axis_narrow_can_serve(const AxisLaunch &a, int type)
 {
     if (!narrow_known(type) || a.wide || a.transposed || a.srcW < VEC || a.maxOutputsPerStrip > 256) return false;
-    if (narrow_is_half(type)) return a.tapStep <= 1 && (a.outStrideA == 1 || a.outStrideA == -1);      // single-channel
+    if (narrow_is_half(type) && a.tapStep <= 1) return a.outStrideA == 1 || a.outStrideA == -1;      // single-channel
+    // Half types with channels: u16's rule, every class kept.  Measured (profiles/half_interleaved_time.txt: 4096^2 -> 4096^2, 2048^2 and
+    // 1024^2 at 0 and 180 degrees, 3 and 4 channels, fp16 and bf16, two runs): the kernel is 0.29-0.58 of the forwarding route's time with
+    // more than 64 outputs in some strip and 0.31-0.36 with at most 64, faster beyond the spread in all 24 rows of both runs (the same
+    // row's medians differ by at most 10 % from run to run).
+    if (narrow_is_half(type)) return true;
     // Measured (profiles/int_time.txt): with more than 64 outputs in some strip (ratios below 4, 1:1, up-sampling) the kernel is 0.54-0.83 of
     // the forwarding route's time for both integer types and every channel count, and with 16-bit elements also at 4:1 (0.72-0.83); with
     // 8-bit elements and at most 64 outputs per strip it is not faster beyond the run's spread (0.80-0.98), so that class forwards.
@@ -480,7 +484,7 @@ hipError_t launch_axis_narrow(const AxisLaunch &a, int type, const void *src, Im
     if (!axis_narrow_can_serve(a, type)) return hipErrorInvalidValue;
     // K1's launch rules for a 1- / 2-byte source (axis_launch_shape): nontemporal loads unless output rows share source rows, output rows
     // per workgroup by the rows of a window and the element size.  The plan's measured shape (tuneRows) is fp32's and is not used.
-    const AxisShapeFacts facts{a.nA, a.nB, a.nStrips, 0, a.maxRowSpan, a.rowsShared, a.maxOutputsPerStrip, 0, narrow_is_half(type) ? 1 : a.tapStep, a.outStrideB, 0, 0,
+    const AxisShapeFacts facts{a.nA, a.nB, a.nStrips, 0, a.maxRowSpan, a.rowsShared, a.maxOutputsPerStrip, 0, a.tapStep, a.outStrideB, 0, 0,
                                (int)narrow_elem_size(type), batch};
     const AxisShape shape = axis_launch_shape(facts);
     if (shape.kernel == AXIS_RUN_NOTHING) return hipSuccess;

@@ -26,6 +26,7 @@
 #include "../../include/aai_adjoint_sample.h"
 #include "../../include/aai_f64.h"
 #include "../../include/aai_half.h"
+#include "../../include/aai_half_interleaved.h"
 #include "../../include/aai_int.h"
 
 using namespace aai::engine;
@@ -588,7 +589,7 @@ int aai_resample_half_batch_device(const aai_request *req, int32_t batch, int32_
     if (batch == 0) { g_lastError.clear(); return AAI_OK; }
     AAI_TRY(require_device());
     AAI_TRY(check_strides(g, 1, src_stride, dst_stride));
-    AAI_TRY(enqueue_half(*req, g, batch, half_dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
+    AAI_TRY(enqueue_half(*req, g, batch, 1, half_dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
     g_lastError.clear();
     return AAI_OK;
 }
@@ -610,9 +611,55 @@ int aai_resample_half_host(const aai_request *req, int32_t half_dtype, const voi
     AAI_HIP(dSrc.alloc(sizeof(uint16_t) * nSrc));
     AAI_HIP(dDst.alloc(sizeof(uint16_t) * nDst));
     AAI_HIP(upload(dSrc, src, src_stride, g.W, g.H, sizeof(uint16_t)));
-    AAI_TRY(enqueue_half(*req, g, 1, half_dtype, dSrc.p, g.W, 0, dDst.p, g.dW, 0, stream));
+    AAI_TRY(enqueue_half(*req, g, 1, 1, half_dtype, dSrc.p, g.W, 0, dDst.p, g.dW, 0, stream));
     AAI_HIP(hipStreamSynchronize(stream));
     AAI_HIP(download(dst, dst_stride, dDst, g.dW, g.dH, sizeof(uint16_t)));
+    return finish(*req, g, layout);
+}
+
+// ---- include/aai_half_interleaved.h: the checks of aai_resample_interleaved_device / _host in their order, like the integer entries
+// below, with the half element type where those entries check their src_dtype
+int aai_resample_half_interleaved_device(const aai_request *req, int32_t batch, int32_t channels, int32_t half_dtype, const void *d_src, int64_t src_stride,
+                                         int64_t src_image_stride, void *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(check_half_dtype(half_dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_row_length(g, channels));
+    if (batch > 0 && g.dW > 0 && g.dH > 0) AAI_TRY(check_pointers(d_src, d_dst));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(check_strides(g, channels, src_stride, dst_stride));
+    AAI_TRY(enqueue_half(*req, g, batch, channels, half_dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_resample_half_interleaved_host(const aai_request *req, int32_t channels, int32_t half_dtype, const void *src, int64_t src_stride, void *dst,
+                                       int64_t dst_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(check_half_dtype(half_dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_pointers(src, dst));
+    AAI_TRY(check_row_length(g, channels));
+    AAI_TRY(check_strides(g, channels, src_stride, dst_stride));
+    AAI_TRY(require_device());
+    const int64_t rowSrc = (int64_t)g.W * channels, rowDst = (int64_t)g.dW * channels;
+    if (!rowDst || !g.dH) return finish(*req, g, layout);
+    DeviceBuffer dSrc, dDst;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dSrc.alloc(sizeof(uint16_t) * (size_t)rowSrc * g.H));
+    AAI_HIP(dDst.alloc(sizeof(uint16_t) * (size_t)rowDst * g.dH));
+    AAI_HIP(upload(dSrc, src, src_stride, rowSrc, g.H, sizeof(uint16_t)));
+    AAI_TRY(enqueue_half(*req, g, 1, channels, half_dtype, dSrc.p, rowSrc, 0, dDst.p, rowDst, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    AAI_HIP(download(dst, dst_stride, dDst, rowDst, g.dH, sizeof(uint16_t)));
     return finish(*req, g, layout);
 }
 

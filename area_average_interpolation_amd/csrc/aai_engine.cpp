@@ -922,7 +922,7 @@ int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, con
     return for_each_adjoint_chunk(batch, dGdst, dstImageStride, dGsrc, srcImageStride, imageBytes, device, stream, name, false, launch);
 }
 
-// ---- the narrow-element paths (include/aai_half.h, include/aai_int.h; aai_axis_narrow.hip)
+// ---- the narrow-element paths (include/aai_half.h, include/aai_half_interleaved.h, include/aai_int.h; aai_axis_narrow.hip)
 // `type`: aai::NarrowType.  `srcType` is what enqueue() reads on the forwarding route and what keys the plan: the caller's u8 / u16
 // image itself, or the dense fp32 scratch a half image is widened into.
 static int enqueue_narrow(const aai_request &rq, const Geometry &g, int batch, int channels, int type, const void *dSrc, int64_t srcStride,
@@ -992,11 +992,11 @@ static int enqueue_narrow(const aai_request &rq, const Geometry &g, int batch, i
     return AAI_OK;
 }
 
-int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride, void *dDst,
-                 int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
+int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int channels, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
+                 void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
 {
     const int type = halfType == AAI_HALF_F16 ? aai::NARROW_F16 : aai::NARROW_BF16;
-    return enqueue_narrow(rq, g, batch, 1, type, dSrc, srcStride, srcImageStride, dDst, dstStride, dstImageStride, stream);
+    return enqueue_narrow(rq, g, batch, channels, type, dSrc, srcStride, srcImageStride, dDst, dstStride, dstImageStride, stream);
 }
 
 int enqueue_int(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,

@@ -221,7 +221,8 @@ int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, con
                         int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
 
 // The narrow-element paths (the caller has checked the arguments, strides included): the element type in, the same type out, every mode.
-//   enqueue_half   include/aai_half.h: fp16 / bf16 images of raw 16-bit elements (halfType = AAI_HALF_F16 / AAI_HALF_BF16), single-channel
+//   enqueue_half   include/aai_half.h (channels = 1) and include/aai_half_interleaved.h: fp16 / bf16 images of raw 16-bit elements
+//                  (halfType = AAI_HALF_F16 / AAI_HALF_BF16) of `channels` interleaved channels
 //   enqueue_int    include/aai_int.h: u8 / u16 images (srcType = SRC_U8 / SRC_U16) of `channels` interleaved channels
 // Both are one body (enqueue_narrow, aai_engine.cpp).  The plan is the forward's own under the key (request, channels) -- the one the
 // forwarding route's enqueue() takes (for a half image: of a packed fp32 source), built on the caller's stream by the first call, which
@@ -233,8 +234,8 @@ int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, con
 //               u8 / u16 itself -- into dense fp32 output scratch, one conversion into the caller's buffer.  Scratch = (half: a dense fp32
 //               source and) a dense fp32 output per image in flight, stream-ordered from the device's pool (for_each_adjoint_chunk's), the
 //               batch in chunks of chunk_images().  aai_last_kernel(): "<fp32 name>+widened" (half), "<fp32 name>+quantized" (integer).
-int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride, void *dDst,
-                 int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
+int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int channels, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
+                 void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
 int enqueue_int(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
                 void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
 

@@ -175,15 +175,15 @@ hipError_t launch_f64_adjoint(const RotLaunch &r, int batch, const double *gdst,
                               hipStream_t stream, const char **kernelName);
 
 // ---- the narrow-element paths (aai_axis_narrow.hip; bodies in aai_half_math.hpp and aai_int_math.hpp): the element type in and out ----
-// The element types of include/aai_half.h (fp16 / bf16, single-channel, images of raw 16-bit elements) and include/aai_int.h (u8 / u16,
-// 1..4 interleaved channels).  The public values AAI_HALF_* and AAI_DTYPE_U* collide, so the engine maps them onto this one.  Strides in elements.
+// The element types of include/aai_half.h and include/aai_half_interleaved.h (fp16 / bf16, images of raw 16-bit elements) and
+// include/aai_int.h (u8 / u16), each with 1..4 interleaved channels.  The public values AAI_HALF_* and AAI_DTYPE_U* collide, so the engine maps them onto this one.  Strides in elements.
 enum NarrowType { NARROW_U8 = 0, NARROW_U16 = 1, NARROW_F16 = 2, NARROW_BF16 = 3 };
 constexpr bool narrow_known(int type) { return type >= NARROW_U8 && type <= NARROW_BF16; }
 constexpr bool narrow_is_half(int type) { return type == NARROW_F16 || type == NARROW_BF16; }
 constexpr size_t narrow_elem_size(int type) { return type == NARROW_U8 ? 1 : 2; }
 // The direct kernel over K1's tables: whether it serves a launch block (static facts of the plan: not wide, the lane axis along dst x,
-// at most 256 outputs per strip, at least four elements in a source row; the half types single-channel; 8-bit elements only with more
-// than 64 outputs in some strip: the measured rule of profiles/int_time.txt) ...
+// at most 256 outputs per strip, at least four elements in a source row; 8-bit elements only with more than 64 outputs in some strip:
+// the measured rule of profiles/int_time.txt; the half types with channels in every class: profiles/half_interleaved_time.txt) ...
 bool axis_narrow_can_serve(const AxisLaunch &a, int type);
 // ... and its launch (hipErrorInvalidValue where it does not).  No scratch.  `batch` <= 65535.  *kernelName: what aai_last_kernel()
 // reports, "aai_axis_half_kernel<f16|bf16>" or "aai_axis_int_kernel<u8|u16>".

@@ -10,7 +10,8 @@ tensor's device and only enqueue work.  ``sampler_backward=True`` makes the bili
 is aai_adjoint_sample_batch_device_f32 (aai_adjoint_sample_interleaved_device_f32 for channels_last tensors).  ``f64=True`` is the
 reference-precision operator on float64 tensors (aai_resample_batch_device_f64 / aai_adjoint_batch_device_f64): differentiable to any order.
 ``half=True`` takes float16 / bfloat16 tensors and returns the same dtype (aai_resample_half_batch_device); its backward widens the
-gradient, runs the fp32 adjoint and rounds once.
+gradient, runs the fp32 adjoint and rounds once.  ``half="channels_last"`` additionally reads a channels_last float16 / bfloat16
+(B, C, H, W) tensor with 2 <= C <= 4 in place (aai_resample_half_interleaved_device) and returns a channels_last tensor.
 
 torch is imported here, not by the package: ``import area_average_interpolation_amd`` works without it.
 """
@@ -146,8 +147,46 @@ class _ResampleHalf(torch.autograd.Function):
         return _adjoint_f32(ctx.rq, ctx.src_shape, ctx.planned, gy).to(ctx.dtype), None, None, None
 
 
-def _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, planned, sampler_backward):
-    """resample(..., half=True): float16 / bfloat16 tensors in, the same dtype out (include/aai_half.h)"""
+class _ResampleHalfInterleaved(torch.autograd.Function):
+    """y = round(W x) on a float16 / bfloat16 (B, C, H, W) tensor dense in torch.channels_last, 2 <= C <= 4: the NHWC storage is the library's
+    interleaved layout, aai_resample_half_interleaved_device reads it in place and y is channels_last in x's dtype.  The plan is the fp32
+    interleaved forward's.  Backward: gy widened to fp32, the backward the fp32 operator runs for a channels_last tensor under the same
+    planned_backward / sampler_backward (_nchw_route: `interleaved` and `planned` are its answer), the gradient rounded once to x's
+    dtype, channels_last."""
+
+    @staticmethod
+    def forward(ctx, x, rq, lay, interleaved, planned):
+        B, C, H, W = x.shape
+        dH, dW = lay.dst_height, lay.dst_width
+        y = torch.empty((B, C, dH, dW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        ctx.rq, ctx.lay, ctx.src_shape, ctx.interleaved, ctx.planned, ctx.dtype = rq, lay, (B, C, H, W), interleaved, planned, x.dtype
+        with torch.cuda.device(x.device):
+            _ensure_prepared(rq, C)
+            if planned and planned != _SAMPLER and ctx.needs_input_grad[0]:
+                if interleaved:
+                    _ensure_adjoint_prepared(rq, "separable" if planned == "separable" else "interleaved")
+                else:
+                    _ensure_prepared(rq)         # the planar backward runs on the single-channel plan
+                    _ensure_adjoint_prepared(rq, "rotated" if planned == "any" and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST) else "planned")
+            api.resample_half_interleaved_device(rq, C, x.data_ptr(), W * C, y.data_ptr(), dW * C, _HALF_DTYPES[x.dtype],
+                                                 stream=torch.cuda.current_stream().cuda_stream, batch=B, src_image_stride=H * W * C,
+                                                 dst_image_stride=dH * dW * C)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        B, C, H, W = ctx.src_shape
+        if ctx.interleaved:
+            gx = _adjoint_interleaved_f32(ctx.rq, ctx.src_shape, ctx.planned, gy)
+        else:
+            gx = _adjoint_f32(ctx.rq, (B * C, H, W), ctx.planned, gy.contiguous().view(B * C, gy.shape[2], gy.shape[3])).view(B, C, H, W)
+        return gx.to(ctx.dtype, memory_format=torch.channels_last), None, None, None, None
+
+
+def _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, planned, sampler_backward, channels_last=False):
+    """resample(..., half=True): float16 / bfloat16 tensors in, the same dtype out (include/aai_half.h); channels_last: half="channels_last",
+    the zero-copy route of include/aai_half_interleaved.h for the tensors that qualify"""
     if x.dtype not in _HALF_DTYPES:
         raise TypeError("resample(half=True) takes a float16 or bfloat16 tensor, got %s" % x.dtype)
     if x.dim() not in (2, 3, 4):
@@ -163,8 +202,11 @@ def _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_an
     sampler = mode not in (L.MODE_AREA, L.MODE_FAST)
     if x.requires_grad and torch.is_grad_enabled() and sampler and not sampler_backward:
         raise ValueError(_NO_SAMPLER_ADJOINT)
+    if (channels_last and x.dim() == 4 and 2 <= x.shape[1] <= 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
+            and lay.dst_height > 0 and lay.dst_width > 0):
+        return _ResampleHalfInterleaved.apply(x, rq, lay, *_nchw_route(True, lay, mode, planned, sampler_backward)), iso
     if planned in ("interleaved", "channels_last"):
-        planned = "any"              # the half path has no interleaved route
+        planned = "any"              # the half=True path has no interleaved route
     if sampler and sampler_backward:
         planned = _SAMPLER
     # every rank through the (B, H, W) operator; a 4-D tensor plane by plane (channels_last and other strided input is made contiguous)
@@ -234,20 +276,26 @@ class _ResampleInterleaved(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        B, C, H, W = ctx.src_shape
-        if gy.dtype != torch.float32:
-            gy = gy.float()
-        gy = gy.contiguous(memory_format=torch.channels_last)
-        gx = torch.empty((B, C, H, W), dtype=torch.float32, device=gy.device, memory_format=torch.channels_last)
-        dH, dW = gy.shape[2], gy.shape[3]
-        with torch.cuda.device(gy.device):
-            if ctx.planned == _SAMPLER:
-                api.adjoint_sample_interleaved_device(ctx.rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, stream=torch.cuda.current_stream().cuda_stream,
-                                                      batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C)
-            else:
-                api.adjoint_interleaved_device(ctx.rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, stream=torch.cuda.current_stream().cuda_stream,
-                                               batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C, planned=ctx.planned)
-        return gx, None, None, None
+        return _adjoint_interleaved_f32(ctx.rq, ctx.src_shape, ctx.planned, gy), None, None, None
+
+
+def _adjoint_interleaved_f32(rq, src_shape, planned, gy):
+    """gx (fp32, (B, C, H, W) channels_last) = W^T gy for a (B, C, dH, dW) gradient of any float dtype and layout: the backward of
+    _ResampleInterleaved and, widened, of _ResampleHalfInterleaved"""
+    B, C, H, W = src_shape
+    if gy.dtype != torch.float32:
+        gy = gy.float()
+    gy = gy.contiguous(memory_format=torch.channels_last)
+    gx = torch.empty((B, C, H, W), dtype=torch.float32, device=gy.device, memory_format=torch.channels_last)
+    dH, dW = gy.shape[2], gy.shape[3]
+    with torch.cuda.device(gy.device):
+        if planned == _SAMPLER:
+            api.adjoint_sample_interleaved_device(rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, stream=torch.cuda.current_stream().cuda_stream,
+                                                  batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C)
+        else:
+            api.adjoint_interleaved_device(rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, stream=torch.cuda.current_stream().cuda_stream,
+                                           batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C, planned=planned)
+    return gx
 
 
 class _ResampleF64(torch.autograd.Function):
@@ -334,28 +382,32 @@ def _resample_nchw(x, geometry, mode, policy, planned, sampler_backward=False):
     if x.requires_grad and torch.is_grad_enabled() and mode not in (L.MODE_AREA, L.MODE_FAST) and not sampler_backward:
         raise ValueError(_NO_SAMPLER_ADJOINT)
     interleaved = 2 <= C <= 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
+    interleaved, planned = _nchw_route(interleaved, lay, mode, planned, sampler_backward)
+    if interleaved:
+        return _ResampleInterleaved.apply(x, rq, lay, planned), iso
+    y = _Resample.apply(x.contiguous().view(B * C, H, W), rq, lay, planned)
+    return y.view(B, C, lay.dst_height, lay.dst_width), iso
+
+
+def _nchw_route(interleaved, lay, mode, planned, sampler_backward):
+    """The route of a (B, C, H, W) fp32 tensor and of its backward (the table in resample()'s docstring).  interleaved: whether the tensor
+    is dense in channels_last with 2 <= C <= 4.  -> (the interleaved route?, `planned` as _ResampleInterleaved / _Resample take it)"""
     if mode not in (L.MODE_AREA, L.MODE_FAST) and sampler_backward:
         # the samplers' adjoint: the route is the forward's (planned_backward chooses between adjoints of the area / fast modes only)
-        if interleaved:
-            return _ResampleInterleaved.apply(x, rq, lay, _SAMPLER), iso
-        y = _Resample.apply(x.contiguous().view(B * C, H, W), rq, lay, _SAMPLER)
-        return y.view(B, C, lay.dst_height, lay.dst_width), iso
+        return interleaved, _SAMPLER
     if planned == "channels_last":
         if interleaved and lay.kernel == L.KERNEL_AXIS:
-            return _ResampleInterleaved.apply(x, rq, lay, "separable"), iso      # zero-copy AND the transposed separable backward
+            return True, "separable"     # zero-copy AND the transposed separable backward
         planned = "interleaved"      # every other input: exactly "interleaved"
     if planned == "interleaved":
         if interleaved and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST):
-            return _ResampleInterleaved.apply(x, rq, lay, "any"), iso       # zero-copy AND the planned backward
+            return True, "any"           # zero-copy AND the planned backward
         planned = "any"              # every other input: exactly "any"
     if interleaved and planned and lay.kernel == L.KERNEL_AXIS:
         interleaved = False          # the planned adjoint is single-channel, and far faster there than the interleaved gather
     if interleaved and planned == "any" and lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST):
         interleaved = False          # ... and so is the planned adjoint at general rotations
-    if interleaved:
-        return _ResampleInterleaved.apply(x, rq, lay), iso
-    y = _Resample.apply(x.contiguous().view(B * C, H, W), rq, lay, planned)
-    return y.view(B, C, lay.dst_height, lay.dst_width), iso
+    return interleaved, (False if interleaved else planned)
 
 
 def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
@@ -452,6 +504,18 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     modes are differentiable ONCE: the backward widens gy to fp32, runs the fp32 adjoint with planned_backward honoured as for an fp32
     tensor ("interleaved" and "channels_last" mean "any": there is no interleaved route), and rounds the gradient to x's dtype;
     bilinear / bicubic with sampler_backward=True likewise.  torch.autocast does not route here by itself.
+    "channels_last" -- exactly True for every input but one: a float16 / bfloat16 (B, C, H, W) tensor dense in torch.channels_last (and not
+    dense in the default format) with 2 <= C <= 4 is read IN PLACE as B interleaved images (include/aai_half_interleaved.h:
+    aai_resample_half_interleaved_device on torch.cuda.current_stream(); the plan is the fp32 interleaved forward's for C channels) and
+    y is channels_last in x's dtype: nothing is copied.  Per channel the values keep half=True's contract; the bits are the interleaved
+    entry's (within one unit in the last place of the planar route's).  The backward widens gy to fp32 channels_last, runs the backward
+    the table above gives an fp32 channels_last tensor under the same planned_backward -- "interleaved" and "channels_last" keep their
+    meaning here, they do not collapse to "any" -- or, bilinear / bicubic with sampler_backward=True,
+    aai_adjoint_sample_interleaved_device_f32, and rounds the gradient once to x's dtype; x.grad is channels_last.
+      half=            channels_last tensor, 2 <= C <= 4        every other tensor
+      True             made contiguous, planar, y contiguous    planar
+      "channels_last"  in place, interleaved, y channels_last   exactly True
+    Any other string raises ValueError.
 
     integer: False (the default) -- nothing changes: a uint8 / uint16 tensor raises TypeError.  True -- the integer operator
     (include/aai_int.h): x must be a torch.uint8 tensor (or torch.uint16 where this torch has that dtype; float32 raises TypeError) on a
@@ -474,6 +538,8 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         planned_backward = positional[0]
     if not isinstance(x, torch.Tensor):
         raise TypeError("resample() takes a torch.Tensor")
+    if isinstance(half, str) and half != "channels_last":
+        raise ValueError('half must be False, True or "channels_last", got %r' % (half,))
     if integer:
         if half or f64 or planned_backward is not False or sampler_backward:
             raise ValueError("resample(integer=True) has no gradient and one element type: it takes none of half, f64, planned_backward, sampler_backward")
@@ -482,7 +548,7 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         return _resample_f64(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     if half:
         return _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, _normalise_planned(planned_backward),
-                              bool(sampler_backward))
+                              bool(sampler_backward), channels_last=half == "channels_last")
     if x.dtype != torch.float32:
         raise TypeError("resample() takes a float32 tensor, got %s" % x.dtype)
     if x.dim() not in (2, 3, 4):

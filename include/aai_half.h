@@ -46,9 +46,9 @@ enum { AAI_HALF_F16 = 1, AAI_HALF_BF16 = 2 };   /* IEEE binary16 / bfloat16, as 
  *               NOT TESTED: whether this route can be recorded into a stream capture (the pool's allocations, like the adjoint's).
  * The two routes agree to one unit in the last place of `half_dtype`: their fp32 sums differ in the order of a few operations.
  *
- * NOT PROVIDED: interleaved channels, row bands, the multi-device entry, a half adjoint in the C ABI (the torch operator widens the
- * gradient and runs the fp32 adjoint), the listed-pixel correction behind the direct kernel (such plans forward), a direct kernel for
- * the transposed quadrants (90 / 270 degrees forward). */
+ * NOT PROVIDED: interleaved channels (by these two entries: aai_half_interleaved.h has them), row bands, the multi-device entry, a
+ * half adjoint in the C ABI (the torch operator widens the gradient and runs the fp32 adjoint), the listed-pixel correction behind the
+ * direct kernel (such plans forward), a direct kernel for the transposed quadrants (90 / 270 degrees forward). */
 int aai_resample_half_batch_device(const aai_request *req, int32_t batch, int32_t half_dtype,
                                    const void *d_src, int64_t src_stride, int64_t src_image_stride,
                                    void *d_dst, int64_t dst_stride, int64_t dst_image_stride, void *stream);

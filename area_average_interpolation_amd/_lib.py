@@ -161,6 +161,13 @@ HALF_INTERLEAVED_SYMBOLS = {
     "aai_resample_half_interleaved_host": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
 }
 
+# the extension header include/aai_adjoint_half.h: the adjoint on fp16 / bf16 gradients of 1..4 interleaved channels (the argument lists of
+# include/aai_adjoint_planned_interleaved.h's entries, the half element type behind the channels)
+ADJOINT_HALF_SYMBOLS = {
+    "aai_adjoint_half_device": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _I64, _I64, _P, _I64, _I64, _P]),
+    "aai_adjoint_half_host": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
+}
+
 _lib = None
 
 
@@ -184,7 +191,7 @@ def load():
         for name, (res, args) in (list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()) + list(INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(ROTATED_ADJOINT_SYMBOLS.items()) + list(ROTATED_INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items()) + list(SAMPLE_ADJOINT_SYMBOLS.items()) + list(F64_SYMBOLS.items()) +
-                                  list(HALF_SYMBOLS.items()) + list(INT_SYMBOLS.items()) + list(HALF_INTERLEAVED_SYMBOLS.items())):
+                                  list(HALF_SYMBOLS.items()) + list(INT_SYMBOLS.items()) + list(HALF_INTERLEAVED_SYMBOLS.items()) + list(ADJOINT_HALF_SYMBOLS.items())):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

@@ -610,6 +610,51 @@ def resample_half_interleaved_host(src, src_resolution, dst_resolution, src_isoc
     return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
 
 
+def adjoint_half_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr, src_stride, half_dtype, stream=0, batch=None, dst_image_stride=0,
+                        src_image_stride=0):
+    """aai_adjoint_half_device (include/aai_adjoint_half.h): gsrc = W(request)^T gdst on device-resident fp16 (half_dtype = HALF_F16) or
+    bf16 (HALF_BF16) gradient images of `channels` = 1..4 interleaved channels, the same element type out -- the transpose of what
+    resample_half_interleaved_device computes (area and fast modes).  Raw device pointers (ints), strides in 2-byte elements, a
+    hipStream_t handle; every element of gsrc is written.  The bits of narrow(adjoint_interleaved_device(widen(gdst)),
+    planned="separable"): at rotations by multiples of 90 degrees on a plan without correction lists ONE launch on the half images
+    (last_kernel(): "aai_axis_adjoint_half_kernel<f16|bf16,C>"), everything else widens into fp32 scratch, runs that entry's launches
+    and narrows ("<fp32 route>+widened").  adjoint_rotated_prepare(request) prepares these calls."""
+    rc = L.load().aai_adjoint_half_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(half_dtype), gdst_ptr, dst_stride,
+                                          dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
+def adjoint_half_host(gdst_bits, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
+                      half_dtype=None):
+    """Host-buffer half-precision adjoint (aai_adjoint_half_host): gdst_bits is the [dH, dW] or [dH, dW, C] (C = 1..4, interleaved)
+    gradient as np.uint16 holding the raw bits of half_dtype (HALF_F16 or HALF_BF16; required), src_shape = (H, W); the bits of
+    adjoint_half_device.  Returns (code, message, gsrc bits [H, W] or [H, W, C] np.uint16, or None)."""
+    lib = L.load()
+    if half_dtype is None:
+        raise ValueError("adjoint_half_host needs half_dtype (HALF_F16 or HALF_BF16): uint16 bits do not name their type")
+    g = np.asarray(gdst_bits)
+    if g.dtype != np.uint16:
+        raise TypeError("adjoint_half_host takes np.uint16 images of raw fp16 / bf16 bits, got %s" % g.dtype)
+    if g.ndim not in (2, 3):
+        raise ValueError("gdst_bits must be a [dH, dW] or [dH, dW, C] array")
+    g = np.ascontiguousarray(g)
+    H, W = int(src_shape[0]), int(src_shape[1])
+    tail = g.shape[2:]
+    C = tail[0] if tail else 1
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None
+    if g.shape[:2] != (lay.dst_height, lay.dst_width):
+        raise ValueError("gdst_bits must have the output's shape %r" % ((lay.dst_height, lay.dst_width) + tail,))
+    gsrc = np.empty((H, W) + tail, dtype=np.uint16)
+    rc = lib.aai_adjoint_half_host(_ref(rq), C, int(half_dtype), g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
+    if rc != L.OK:
+        return rc, last_error(), None
+    return rc, "", gsrc
+
+
 def resample_int_device(request, channels, src_ptr, src_stride, dst_ptr, dst_stride, dtype, stream=0, batch=None, src_image_stride=0, dst_image_stride=0):
     """aai_resample_int_batch_device (include/aai_int.h): the forward on device-resident 8-bit (dtype = DTYPE_U8) or 16-bit (DTYPE_U16)
     unsigned images of `channels` = 1..4 interleaved channels, which writes the SAME element type: every source element as its integer

@@ -27,6 +27,7 @@
 #include "../../include/aai_f64.h"
 #include "../../include/aai_half.h"
 #include "../../include/aai_half_interleaved.h"
+#include "../../include/aai_adjoint_half.h"
 #include "../../include/aai_int.h"
 
 using namespace aai::engine;
@@ -114,12 +115,15 @@ int check_adjoint_sample_request(const aai_request *rq, int batch, aai::Geometry
 // ... and the images'.  The interleaved entries (aai_adjoint_interleaved_*, aai_adjoint_rotated_interleaved_*, aai_adjoint_planned_interleaved_*) check the channel count
 // right after the request, as the forward's interleaved entries report it, and the row length before the pointers; the single-channel
 // entries check neither.  Strides in elements of `channels` per pixel.
+int check_half_dtype(int32_t dtype);
+// (halfDtype: the element type of the entries of include/aai_adjoint_half.h, checked directly behind the channel count; the fp32 entries pass none)
 int check_adjoint(AdjointFamily family, const aai_request *rq, int batch, bool interleaved, int channels, const void *gdst, int64_t dstStride,
-                  const void *gsrc, int64_t srcStride, aai::Geometry &g)
+                  const void *gsrc, int64_t srcStride, aai::Geometry &g, const int32_t *halfDtype = nullptr)
 {
     if (interleaved) {
         AAI_TRY(check_request(rq));
         AAI_TRY(check_channels(channels));
+        if (halfDtype) AAI_TRY(check_half_dtype(*halfDtype));
     }
     AAI_TRY(family == ADJOINT_SAMPLE ? check_adjoint_sample_request(rq, batch, g) : check_adjoint_request(rq, batch, g));
     if (interleaved) AAI_TRY(check_row_length(g, channels));
@@ -776,6 +780,39 @@ int aai_adjoint_planned_interleaved_f32(const aai_request *req, int32_t channels
                                         aai_layout *layout)
 {
     return adjoint_host(ADJOINT_SEPARABLE, true, req, channels, gdst, dst_stride, gsrc, src_stride, layout);
+}
+
+// ---- include/aai_adjoint_half.h: the checks of aai_adjoint_planned_interleaved_device_f32 / _f32 (check_adjoint) with the element type
+// directly behind the channel count
+int aai_adjoint_half_device(const aai_request *req, int32_t batch, int32_t channels, int32_t half_dtype, const void *d_gdst, int64_t dst_stride,
+                            int64_t dst_image_stride, void *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint(ADJOINT_SEPARABLE, req, batch, true, channels, d_gdst, dst_stride, d_gsrc, src_stride, g, &half_dtype));
+    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
+    AAI_TRY(require_device());
+    AAI_TRY(enqueue_adjoint_half(*req, g, batch, channels, half_dtype, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride,
+                                 (hipStream_t)stream));
+    g_lastError.clear();
+    return AAI_OK;
+}
+
+int aai_adjoint_half_host(const aai_request *req, int32_t channels, int32_t half_dtype, const void *gdst, int64_t dst_stride, void *gsrc, int64_t src_stride,
+                          aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_adjoint(ADJOINT_SEPARABLE, req, 1, true, channels, gdst, dst_stride, gsrc, src_stride, g, &half_dtype));
+    AAI_TRY(require_device());
+    const int64_t rowDst = (int64_t)g.dW * channels, rowSrc = (int64_t)g.W * channels;
+    DeviceBuffer dGdst, dGsrc;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dGdst.alloc(sizeof(uint16_t) * (size_t)rowDst * g.dH));
+    AAI_HIP(dGsrc.alloc(sizeof(uint16_t) * (size_t)rowSrc * g.H));
+    AAI_HIP(upload(dGdst, gdst, dst_stride, rowDst, g.dH, sizeof(uint16_t)));
+    AAI_TRY(enqueue_adjoint_half(*req, g, 1, channels, half_dtype, dGdst.p, rowDst, 0, dGsrc.p, rowSrc, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    AAI_HIP(download(gsrc, src_stride, dGsrc, rowSrc, g.H, sizeof(uint16_t)));
+    return finish(*req, g, layout);
 }
 
 int aai_adjoint_sample_batch_device_f32(const aai_request *req, int32_t batch,

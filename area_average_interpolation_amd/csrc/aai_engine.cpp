@@ -806,6 +806,21 @@ static int acquire_rot_adjoint_plan(const aai_request &rq, const Geometry &g, bo
     return build_rot_adjoint_tables(**out);
 }
 
+// the argument block of the transposed separable kernels for a single-channel plan with its adjoint tables, a channel count and a dst row
+// stride (elements): the forward's mapping (make_axis_launch) of (ka, kb) onto the first element of a dst PIXEL of `channels` elements
+static aai::AxisAdjointLaunch make_axis_adjoint_launch(const Plan &p, int channels, int64_t dstStride)
+{
+    const aai::AxisTables &t = p.tabs;
+    const int64_t sa = t.transposed ? dstStride : channels, sb = t.transposed ? channels : dstStride;
+    aai::AxisAdjointLaunch a{};
+    a.laneTab = p.dLane; a.rowTab = p.dRow; a.colRange = p.dColRange; a.rowRange = p.dRowRange;
+    a.srcW = p.g.W; a.srcH = p.g.H;
+    a.outStrideA = t.flipA ? -sa : sa;
+    a.outStrideB = t.flipB ? -sb : sb;
+    a.outBase = (t.flipA ? (int64_t)(t.nA - 1) * sa : 0) + (t.flipB ? (int64_t)(t.nB - 1) * sb : 0);
+    return a;
+}
+
 int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry &g, int batch, int channels, const float *dGdst, int64_t dstStride,
                     int64_t dstImageStride, float *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
 {
@@ -849,13 +864,7 @@ int enqueue_adjoint(AdjointFamily family, const aai_request &rq, const Geometry 
     if (family == ADJOINT_PLANNED || family == ADJOINT_SEPARABLE) {
         // (ka, kb) -> the first element of a dst PIXEL: the forward's mapping (make_axis_launch) with a pixel of `channels` elements.  Not
         // make_axis_launch(*p, channels, ...): that divides the plan's nA by the channel count, and this plan's nA is in pixels already.
-        const aai::AxisTables &t = p->tabs;
-        const int64_t sa = t.transposed ? dstStride : channels, sb = t.transposed ? channels : dstStride;
-        a.laneTab = p->dLane; a.rowTab = p->dRow; a.colRange = p->dColRange; a.rowRange = p->dRowRange;
-        a.srcW = g.W; a.srcH = g.H;
-        a.outStrideA = t.flipA ? -sa : sa;
-        a.outStrideB = t.flipB ? -sb : sb;
-        a.outBase = (t.flipA ? (int64_t)(t.nA - 1) * sa : 0) + (t.flipB ? (int64_t)(t.nB - 1) * sb : 0);
+        a = make_axis_adjoint_launch(*p, channels, dstStride);
         name = "aai_axis_adjoint_kernel";            // (SEPARABLE: its launcher names the instantiation)
         listed = p->adjSrcCount != 0 && p->adjDstCount != 0;
         if (!listed) imageBytes = 0;     // the transposed separable kernels need no scratch, only the correction pass does
@@ -987,6 +996,81 @@ static int enqueue_narrow(const aai_request &rq, const Geometry &g, int batch, i
     const hipError_t ef = hipFreeAsync(scratch, stream);
     if (rl != AAI_OK) return fail(rl, lastError);
     g_lastKernel += half ? "+widened" : "+quantized";
+    if (e != hipSuccess) return hip_fail(e, what);
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    return AAI_OK;
+}
+
+// ---- the half-precision adjoint (include/aai_adjoint_half.h; aai_axis_adjoint_narrow.hip): routes in aai_engine.hpp
+int enqueue_adjoint_half(const aai_request &rq, const Geometry &g, int batch, int channels, int halfType, const void *dGdst, int64_t dstStride,
+                         int64_t dstImageStride, void *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream)
+{
+    const int type = halfType == AAI_HALF_F16 ? aai::NARROW_F16 : aai::NARROW_BF16;
+    const char *gd = static_cast<const char *>(dGdst);
+    char *gs = static_cast<char *>(dGsrc);
+    const int64_t elem = (int64_t)aai::narrow_elem_size(type);
+    const aai::ImageView dv{dstStride, dstImageStride}, sv{srcStride, srcImageStride};
+    if (pick_kernel(rq, g) == AAI_KERNEL_AXIS) {
+        // the forward's single-channel plan with the adjoint tables of PLANNED / SEPARABLE: what enqueue_adjoint acquires for them, and
+        // what aai_adjoint_rotated_prepare builds
+        PlanRef p;
+        const int rc = acquire_plan(rq, g, -1, -1, 1, aai::ROT_FORM_QUAD, &p, /*onCallerStream*/ true, stream);
+        if (rc != AAI_OK) return rc;
+        {
+            std::lock_guard<std::mutex> lock(p->build);
+            const int rt = build_adjoint_tables(*p);
+            if (rt != AAI_OK) return rt;
+        }
+        // DIRECT: the tables are there, the plan has no lists for a correction pass, and the request is of a class whose direct launch
+        // was measured faster than the forwarding route's stages (profiles/adjoint_half_time.txt: every class but one -- a single
+        // channel, up-sampling, at 90 / 270 degrees, where the kernel is bound by its strided 2-byte gdst loads and gains nothing over the
+        // fp32 kernel: 187 against 184 us for 2048^2 <- 4096^2).  Tables and launch block are read-only here: no scratch, no side stream,
+        // no event, hence no lock.
+        const bool loses = channels == 1 && p->tabs.transposed && (int64_t)g.dW * g.dH > (int64_t)g.W * g.H;
+        if (p->adjState == 1 && !(p->adjSrcCount != 0 && p->adjDstCount != 0) && !loses) {
+            const aai::AxisAdjointLaunch a = make_axis_adjoint_launch(*p, channels, dstStride);
+            const char *name = "";
+            hipError_t e = hipSuccess;
+            for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridZ)      // grid.z carries the batch
+                e = aai::launch_axis_adjoint_half(a, type, channels, std::min(batch - b0, kMaxGridZ), gd + (int64_t)b0 * dstImageStride * elem, dv,
+                                                  gs + (int64_t)b0 * srcImageStride * elem, sv, stream, &name);
+            g_lastKernel = name;
+            if (e != hipSuccess) return hip_fail(e, name);
+            return AAI_OK;
+        }
+    }
+    // FORWARDING: widen gdst into dense fp32 scratch, the code behind aai_adjoint_planned_interleaved_device_f32 into a dense fp32 gsrc,
+    // one rounding into the caller's buffer -- the bits of narrow(fp32 entry(widen(gdst)))
+    const int64_t rowDst = (int64_t)g.dW * channels, rowSrc = (int64_t)g.W * channels;
+    const size_t nDst = (size_t)rowDst * (size_t)g.dH, nSrc = (size_t)rowSrc * (size_t)g.H;
+    const size_t dstBytes = (nDst * sizeof(float) + 255) & ~(size_t)255, srcBytes = (nSrc * sizeof(float) + 255) & ~(size_t)255;
+    const int chunk = chunk_images(batch, dstBytes + srcBytes);
+    int device = 0;
+    AAI_HIP(hipGetDevice(&device));
+    hipMemPool_t pool = nullptr;
+    const int rp = adjoint_scratch_pool(device, &pool);
+    if (rp != AAI_OK) return rp;
+    char *scratch = nullptr;
+    AAI_HIP(hipMallocFromPoolAsync((void **)&scratch, (dstBytes + srcBytes) * (size_t)chunk, pool, stream));
+    // (dense fp32 images, image b of a chunk at b * nDst / b * nSrc: all the widened gradients of a chunk, then all its results)
+    float *d32 = reinterpret_cast<float *>(scratch), *s32 = reinterpret_cast<float *>(scratch + dstBytes * (size_t)chunk);
+    const char *what = "aai_half_widen_kernel";
+    hipError_t e = hipSuccess;
+    int rl = AAI_OK;
+    for (int b0 = 0; b0 < batch && e == hipSuccess && rl == AAI_OK; b0 += chunk) {
+        const int nb = std::min(batch - b0, chunk);
+        what = "aai_half_widen_kernel";
+        if (nDst) e = aai::launch_narrow_widen(type, gd + (int64_t)b0 * dstImageStride * elem, dv, d32, (int)rowDst, g.dH, nb, stream);
+        if (e != hipSuccess) break;
+        rl = enqueue_adjoint(ADJOINT_SEPARABLE, rq, g, nb, channels, d32, rowDst, (int64_t)nDst, s32, rowSrc, (int64_t)nSrc, stream);
+        if (rl != AAI_OK) break;
+        what = "aai_half_narrow_kernel";
+        e = aai::launch_narrow_store(type, s32, gs + (int64_t)b0 * srcImageStride * elem, sv, (int)rowSrc, g.H, nb, stream);
+    }
+    const std::string lastError = g_lastError;      // (of a failed enqueue_adjoint(): hipFreeAsync below must not replace it)
+    const hipError_t ef = hipFreeAsync(scratch, stream);
+    if (rl != AAI_OK) return fail(rl, lastError);
+    g_lastKernel += "+widened";
     if (e != hipSuccess) return hip_fail(e, what);
     if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     return AAI_OK;

@@ -239,6 +239,22 @@ int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int channe
 int enqueue_int(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
                 void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
 
+// The half-precision adjoint (include/aai_adjoint_half.h; the caller has checked the arguments): gsrc = narrow(W^T widen(gdst)) for `batch`
+// fp16 / bf16 images (halfType = AAI_HALF_F16 / AAI_HALF_BF16) of raw 16-bit elements with `channels` = 1..4 interleaved channels, area /
+// fast modes, strides in elements.  On both routes the bits of narrow(enqueue_adjoint(ADJOINT_SEPARABLE, widen(gdst))).  The plan is
+// SEPARABLE's: the forward's single-channel plan with its adjoint tables, built on first need (that blocks; aai_adjoint_rotated_prepare
+// builds the same).  Two routes, chosen by static facts of the plan:
+//   DIRECT      pick_kernel() says AXIS (rotations by 0 / 90 / 180 / 270 degrees), the plan holds its adjoint tables (adjState 1) and has
+//               no lists for a correction pass -- but for the one class that measured no faster than forwarding, a single channel
+//               up-sampled (more dst than source pixels) at 90 / 270 degrees (profiles/adjoint_half_time.txt) --: one launch of aai_axis_adjoint_half_kernel<HT, C> on the caller's images, no scratch, no
+//               lock, the batch split at kMaxGridZ.  aai_last_kernel(): "aai_axis_adjoint_half_kernel<f16|bf16,C>".
+//   FORWARDING  everything else (general rotations, wide or dense plans, refused inversions, plans with lists): gdst widened into dense
+//               fp32 scratch, enqueue_adjoint(ADJOINT_SEPARABLE) into a dense fp32 gsrc, one rounding into the caller's buffer.  Scratch =
+//               a dense fp32 gdst and gsrc per image in flight (beside enqueue_adjoint's own), stream-ordered from the device's pool, the
+//               batch in chunks of chunk_images().  aai_last_kernel(): "<the fp32 route's name>+widened".
+int enqueue_adjoint_half(const aai_request &rq, const Geometry &g, int batch, int channels, int halfType, const void *dGdst, int64_t dstStride,
+                         int64_t dstImageStride, void *dGsrc, int64_t srcStride, int64_t srcImageStride, hipStream_t stream);
+
 }  // namespace engine
 
 }  // namespace aai

@@ -196,4 +196,11 @@ hipError_t launch_narrow_widen(int type, const void *src, ImageView sv, float *d
 // of the type: half_narrow or int_quantize.  `batch` <= 65535.
 hipError_t launch_narrow_store(int type, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream);
 
+// ---- the half-precision transposed separable kernel (aai_axis_adjoint_narrow.hip; body in aai_axis_adjoint_half_math.hpp) ----
+// launch_axis_adjoint_multi's launch block (a.srcW / a.srcH in pixels, the mapping of PIXELS onto elements of gdst, the single-channel
+// plan's tables) for `channels` = 1..4 on fp16 / bf16 images (`type`: NARROW_F16 / NARROW_BF16) of raw 16-bit elements: the bits of
+// narrow(launch_axis_adjoint[_multi](widen(gdst))).  No scratch.  `batch` <= 65535.  *kernelName: "aai_axis_adjoint_half_kernel<f16|bf16,C>".
+hipError_t launch_axis_adjoint_half(const AxisAdjointLaunch &a, int type, int channels, int batch, const void *gdst, ImageView dv, void *gsrc, ImageView sv,
+                                    hipStream_t stream, const char **kernelName);
+
 }  // namespace aai

@@ -52,7 +52,7 @@ _ADJOINT_TABLES = {
 }
 
 
-def _ensure_adjoint_prepared(rq, route):
+def _ensure_adjoint_prepared(rq, route, asked=None):
     """The first call of a planned adjoint per (geometry, device) builds the plan's adjoint tables and synchronises (aai_adjoint_prepare,
     aai_adjoint_rotated_prepare): do that in the forward, outside any stream capture.  Inside a capture missing tables are an error,
     not a hidden synchronisation."""
@@ -60,9 +60,9 @@ def _ensure_adjoint_prepared(rq, route):
     if not missing(api.plan_shape(rq, 1).split()):
         return
     if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("resample(planned_backward=%s): this geometry has no adjoint tables on this device yet and the current "
+        raise RuntimeError("resample(%s): this geometry has no adjoint tables on this device yet and the current "
                            "stream is being captured; call resample() (or %s()) once with the same geometry before capturing"
-                           % (shown, prepare.__name__))
+                           % (asked or "planned_backward=%s" % shown, prepare.__name__))
     prepare(rq)
 
 
@@ -184,7 +184,54 @@ class _ResampleHalfInterleaved(torch.autograd.Function):
         return gx.to(ctx.dtype, memory_format=torch.channels_last), None, None, None, None
 
 
-def _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, planned, sampler_backward, channels_last=False):
+class _ResampleHalfNarrowBackward(torch.autograd.Function):
+    """resample(..., half=..., half_backward=True): the forward of _ResampleHalf (x a contiguous (B, H, W) tensor, interleaved=False) or of
+    _ResampleHalfInterleaved (x a (B, C, H, W) tensor dense in channels_last, interleaved=True), and a backward that stays in x's dtype:
+    gy goes straight to aai_adjoint_half_device (include/aai_adjoint_half.h) and its output is x.grad -- no fp32 copy of gy, no fp32 gx,
+    no conversion.  The gradient has the bits of the widening backward under planned_backward="any" (planar) / "channels_last"
+    (interleaved): narrow(fp32 planned adjoint(widen(gy)))."""
+
+    @staticmethod
+    def forward(ctx, x, rq, lay, interleaved):
+        B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+        C = x.shape[1] if interleaved else 1
+        dH, dW = lay.dst_height, lay.dst_width
+        if interleaved:
+            y = torch.empty((B, C, dH, dW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        else:
+            y = torch.empty((B, dH, dW), dtype=x.dtype, device=x.device)
+        ctx.rq, ctx.src_shape, ctx.interleaved, ctx.dtype = rq, tuple(x.shape), interleaved, x.dtype
+        if dH and dW:
+            with torch.cuda.device(x.device):
+                _ensure_prepared(rq, C)
+                if ctx.needs_input_grad[0]:
+                    # the adjoint tables live on the single-channel plan: at multiples of 90 degrees those of the transposed separable kernel,
+                    # at a general rotation the sums of the forwarding route's planned adjoint (aai_adjoint_rotated_prepare builds either)
+                    _ensure_adjoint_prepared(rq, "interleaved" if lay.kernel in (L.KERNEL_ROTATED, L.KERNEL_FAST) else "separable", "half_backward=True")
+                api.resample_half_interleaved_device(rq, C, x.data_ptr(), W * C, y.data_ptr(), dW * C, _HALF_DTYPES[x.dtype],
+                                                     stream=torch.cuda.current_stream().cuda_stream, batch=B, src_image_stride=H * W * C,
+                                                     dst_image_stride=dH * dW * C)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        B, H, W = ctx.src_shape[0], ctx.src_shape[-2], ctx.src_shape[-1]
+        C = ctx.src_shape[1] if ctx.interleaved else 1
+        dH, dW = gy.shape[-2], gy.shape[-1]
+        if gy.dtype != ctx.dtype:
+            gy = gy.to(ctx.dtype)
+        gy = gy.contiguous(memory_format=torch.channels_last) if ctx.interleaved else gy.contiguous()
+        if not (dH and dW):
+            return torch.zeros(ctx.src_shape, dtype=ctx.dtype, device=gy.device), None, None, None
+        gx = torch.empty(ctx.src_shape, dtype=ctx.dtype, device=gy.device, memory_format=torch.channels_last if ctx.interleaved else torch.contiguous_format)
+        with torch.cuda.device(gy.device):
+            api.adjoint_half_device(ctx.rq, C, gy.data_ptr(), dW * C, gx.data_ptr(), W * C, _HALF_DTYPES[ctx.dtype],
+                                    stream=torch.cuda.current_stream().cuda_stream, batch=B, dst_image_stride=dH * dW * C, src_image_stride=H * W * C)
+        return gx, None, None, None
+
+
+def _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, planned, sampler_backward, channels_last=False, half_backward=False):
     """resample(..., half=True): float16 / bfloat16 tensors in, the same dtype out (include/aai_half.h); channels_last: half="channels_last",
     the zero-copy route of include/aai_half_interleaved.h for the tensors that qualify"""
     if x.dtype not in _HALF_DTYPES:
@@ -204,13 +251,18 @@ def _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_an
         raise ValueError(_NO_SAMPLER_ADJOINT)
     if (channels_last and x.dim() == 4 and 2 <= x.shape[1] <= 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
             and lay.dst_height > 0 and lay.dst_width > 0):
+        if half_backward:
+            return _ResampleHalfNarrowBackward.apply(x, rq, lay, True), iso
         return _ResampleHalfInterleaved.apply(x, rq, lay, *_nchw_route(True, lay, mode, planned, sampler_backward)), iso
     if planned in ("interleaved", "channels_last"):
         planned = "any"              # the half=True path has no interleaved route
     if sampler and sampler_backward:
         planned = _SAMPLER
     # every rank through the (B, H, W) operator; a 4-D tensor plane by plane (channels_last and other strided input is made contiguous)
-    y = _ResampleHalf.apply(x.contiguous().view(-1, H, W), rq, lay, planned)
+    if half_backward:
+        y = _ResampleHalfNarrowBackward.apply(x.contiguous().view(-1, H, W), rq, lay, False)
+    else:
+        y = _ResampleHalf.apply(x.contiguous().view(-1, H, W), rq, lay, planned)
     return y.view(lead + (lay.dst_height, lay.dst_width)), iso
 
 
@@ -411,7 +463,7 @@ def _nchw_route(interleaved, lay, mode, planned, sampler_backward):
 
 
 def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
-             *positional, sampler_backward=False, f64=False, half=False, integer=False, planned_backward=False):
+             *positional, sampler_backward=False, f64=False, half=False, integer=False, half_backward=False, planned_backward=False):
     """Resample a CUDA/HIP fp32 tensor of shape (H, W), (B, H, W) or (B, C, H, W); returns ``(y, dst_isocenter)`` with y of shape
     (dH, dW), (B, dH, dW) or (B, C, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
     bilinear / bicubic comparison paths are differentiable only with sampler_backward=True, below: without it an x that requires grad
@@ -517,6 +569,18 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
       "channels_last"  in place, interleaved, y channels_last   exactly True
     Any other string raises ValueError.
 
+    half_backward: False (the default) -- nothing changes.  True (keyword-only; needs half=True or half="channels_last", an area or fast
+    mode and planned_backward left at False: anything else raises ValueError) -- the forward is half's, and the backward stays in x's
+    dtype: gy, made dense in y's layout, goes straight to aai_adjoint_half_device (include/aai_adjoint_half.h) on
+    torch.cuda.current_stream() and what that writes is x.grad -- no fp32 copy of gy, no fp32 gradient image, no conversion kernel.  At
+    rotations by multiples of 90 degrees (plans without correction lists) that is ONE kernel on the half tensors; every other request --
+    and one class that measured no faster that way, a single-channel image up-sampled at 90 / 270 degrees
+    (profiles/adjoint_half_time.txt) -- widens into the library's scratch, runs the fp32 planned adjoint and narrows: the same bits.  Planar tensors of any rank go as B * C single-channel
+    images and x.grad has the bits of half=True, planned_backward="any"; a channels_last tensor that half="channels_last" reads in place
+    goes as B interleaved images, x.grad is channels_last and has the bits of half="channels_last", planned_backward="channels_last".  With
+    an x that requires grad the forward builds the single-channel plan's adjoint tables (aai_adjoint_rotated_prepare; it synchronises once
+    per geometry and device), so inside a stream capture a geometry without them raises RuntimeError.  Differentiable ONCE.
+
     integer: False (the default) -- nothing changes: a uint8 / uint16 tensor raises TypeError.  True -- the integer operator
     (include/aai_int.h): x must be a torch.uint8 tensor (or torch.uint16 where this torch has that dtype; float32 raises TypeError) on a
     GPU, of shape (H, W), (B, H, W) or (B, C, H, W) with C <= 4; y has x's dtype.  The forward is aai_resample_int_batch_device on
@@ -540,6 +604,13 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         raise TypeError("resample() takes a torch.Tensor")
     if isinstance(half, str) and half != "channels_last":
         raise ValueError('half must be False, True or "channels_last", got %r' % (half,))
+    if half_backward:
+        if not half:
+            raise ValueError('resample(half_backward=True) needs half=True or half="channels_last": it is the backward of the half-precision operator')
+        if planned_backward is not False:
+            raise ValueError("resample(half_backward=True) names its backward itself: planned_backward must stay False, got %r" % (planned_backward,))
+        if mode not in (L.MODE_AREA, L.MODE_FAST):
+            raise ValueError("resample(half_backward=True): the area and fast modes only (the samplers' adjoint has no half-precision entry)")
     if integer:
         if half or f64 or planned_backward is not False or sampler_backward:
             raise ValueError("resample(integer=True) has no gradient and one element type: it takes none of half, f64, planned_backward, sampler_backward")
@@ -548,7 +619,7 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         return _resample_f64(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     if half:
         return _resample_half(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, _normalise_planned(planned_backward),
-                              bool(sampler_backward), channels_last=half == "channels_last")
+                              bool(sampler_backward), channels_last=half == "channels_last", half_backward=bool(half_backward))
     if x.dtype != torch.float32:
         raise TypeError("resample() takes a float32 tensor, got %s" % x.dtype)
     if x.dim() not in (2, 3, 4):

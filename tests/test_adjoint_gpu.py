@@ -14,6 +14,7 @@ import pytest
 
 from conftest import TOL
 from adjoint_columns import comb_cases, comb_gold_pixels, comb_pitch, edge_phases
+from grid_carry_cases import rows_pixels as _rows_pixels
 from test_adjoint_host import EIGHT, adjoint_gold, assert_adjoint_matches, oracle_matrix
 
 pytestmark = pytest.mark.gpu
@@ -380,16 +381,6 @@ def test_adjoint_per_pixel_at_size(gpu, po, name):
         assert not image.any()
         del gd, gs
     torch.cuda.empty_cache()
-
-
-def _rows_pixels(W, rows, seed):
-    """every listed row at columns 0, 15, 16, W-1 and two seeded ones"""
-    rng = np.random.default_rng(seed)
-    px = []
-    for r in rows:
-        cols = [0, 15, 16, W - 1] + [int(c) for c in rng.integers(1, W - 1, 2)]
-        px += [(c, r) for c in dict.fromkeys(c for c in cols if 0 <= c < W)]
-    return np.array([p[0] for p in px]), np.array([p[1] for p in px])
 
 
 def test_adjoint_taller_than_one_grid(gpu, po):

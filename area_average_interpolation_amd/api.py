@@ -57,6 +57,11 @@ def last_error():
     return L.load().aai_last_error().decode()
 
 
+def _check(rc):
+    if rc != L.OK:
+        raise AaiError(rc, last_error())
+
+
 def query(request):
     """aai_query: validate + output layout.  Returns (code, message, Layout-or-None).  Needs no GPU."""
     lib = L.load()
@@ -74,19 +79,33 @@ def device_count():
 
 
 def set_device(ordinal):
-    rc = L.load().aai_set_device(int(ordinal))
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_set_device(int(ordinal)))
 
 
 def synchronize():
-    rc = L.load().aai_device_synchronize()
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_device_synchronize())
 
 
 def last_kernel():
     return L.load().aai_last_kernel().decode()
+
+
+def _host_forward(a, channels, channel_axis, geometry, entry, *lead, out_dtype=None):
+    """Every host forward entry on the prepared image a = [H, W] or [H, W, C], C-contiguous: entry(request, *lead, src, src stride, dst,
+    dst stride, layout), strides in elements.  geometry: (src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy);
+    channel_axis: the result is [dH, dW, C]; out_dtype: the result's element type where it is not a's.
+    Returns (code, message, dst or None, (dstIsoX, dstIsoY) or None, Layout or None)."""
+    H, W = a.shape[:2]
+    rq = make_request(W, H, *geometry)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None, None, None
+    dst = np.empty((lay.dst_height, lay.dst_width) + ((channels,) if channel_axis else ()), dtype=out_dtype or a.dtype)
+    out_lay = L.Layout()
+    rc = entry(_ref(rq), *lead, a.ctypes.data, max(W * channels, 1), dst.ctypes.data, max(lay.dst_width * channels, 1), ctypes.byref(out_lay))
+    if rc != L.OK:
+        return rc, last_error(), None, None, None
+    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
 
 
 def resample_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle,
@@ -96,40 +115,18 @@ def resample_host(src, src_resolution, dst_resolution, src_isocenter, rotation_a
     Returns (code, message, dst ndarray or None, (dstIsoX, dstIsoY) or None, Layout or None)."""
     lib = L.load()
     a = np.asarray(src)
+    geometry = (src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     if a.ndim == 2 and a.dtype in (np.uint8, np.uint16):
-        # typed entry (aai_resample_host): 8/16-bit source, fp32 output
-        a = np.ascontiguousarray(a)
-        H, W = a.shape
-        rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-        rc, msg, lay = query(rq)
-        if rc != L.OK:
-            return rc, msg, None, None, None
-        dst = np.empty((lay.dst_height, lay.dst_width), dtype=np.float32)
-        out_lay = L.Layout()
-        rc = lib.aai_resample_host(_ref(rq), a.ctypes.data, L.DTYPE_U8 if a.dtype == np.uint8 else L.DTYPE_U16, W,
-                                   dst.ctypes.data, max(lay.dst_width, 1), ctypes.byref(out_lay))
-        if rc != L.OK:
-            return rc, last_error(), None, None, None
-        return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+        # typed entry (aai_resample_host): 8/16-bit source, fp32 output; the element type goes behind the source pointer
+        dt = L.DTYPE_U8 if a.dtype == np.uint8 else L.DTYPE_U16
+        return _host_forward(np.ascontiguousarray(a), 1, False, geometry, lambda rq, s, *rest: lib.aai_resample_host(rq, s, dt, *rest), out_dtype=np.float32)
     if a.ndim != 2:
         if a.size != 0:
             raise ValueError("src must be a 2-D image [H, W] (interleaved [H, W, C] images: resample_interleaved_host)")
         a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
     if a.dtype != np.float32:
         a = a.astype(np.float64, copy=False)
-    a = np.ascontiguousarray(a)
-    H, W = (a.shape[0], a.shape[1]) if a.ndim == 2 else (0, 0)
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None, None, None
-    dst = np.empty((lay.dst_height, lay.dst_width), dtype=a.dtype)
-    fn = lib.aai_resample_f32 if a.dtype == np.float32 else lib.aai_resample_f64
-    out_lay = L.Layout()
-    rc = fn(_ref(rq), a.ctypes.data, W, dst.ctypes.data, max(lay.dst_width, 1), ctypes.byref(out_lay))
-    if rc != L.OK:
-        return rc, last_error(), None, None, None
-    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+    return _host_forward(np.ascontiguousarray(a), 1, False, geometry, lib.aai_resample_f32 if a.dtype == np.float32 else lib.aai_resample_f64)
 
 
 def precision_check(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
@@ -162,9 +159,7 @@ class _PinnedBlock:
 
     def __init__(self, nbytes):
         self.ptr = ctypes.c_void_p()
-        rc = L.load().aai_host_alloc(ctypes.byref(self.ptr), nbytes)
-        if rc != L.OK:
-            raise AaiError(rc, last_error())
+        _check(L.load().aai_host_alloc(ctypes.byref(self.ptr), nbytes))
 
     def __del__(self):
         ptr, self.ptr = getattr(self, "ptr", None), None
@@ -233,28 +228,19 @@ def resample_interleaved_host(src, src_resolution, dst_resolution, src_isocenter
     a = np.ascontiguousarray(src)
     if a.ndim != 3 or a.dtype not in _NP_DTYPES:
         raise ValueError("src must be an [H, W, C] array of float32, uint8 or uint16")
-    H, W, C = a.shape
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None, None
-    dst = np.empty((lay.dst_height, lay.dst_width, C), dtype=np.float32)
-    out_lay = L.Layout()
-    rc = lib.aai_resample_interleaved_host(_ref(rq), C, a.ctypes.data, _NP_DTYPES[a.dtype], W * C,
-                                           dst.ctypes.data, max(lay.dst_width * C, 1), ctypes.byref(out_lay))
-    if rc != L.OK:
-        return rc, last_error(), None, None
-    return rc, "", dst, out_lay
+    C = a.shape[2]
+    # (the element type goes behind the source pointer)
+    rc, msg, dst, _, out_lay = _host_forward(a, C, True, (src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy),
+                                             lambda rq, s, *rest: lib.aai_resample_interleaved_host(rq, C, s, _NP_DTYPES[a.dtype], *rest), out_dtype=np.float32)
+    return rc, msg, dst, out_lay
 
 
 def resample_interleaved_device(request, channels, src_ptr, src_stride, dst_ptr, dst_stride, stream=0, batch=1,
                                 src_image_stride=0, dst_image_stride=0, src_dtype=L.DTYPE_F32):
     """Device-resident interleaved images (aai_resample_interleaved_device); strides in elements."""
     lib = L.load()
-    rc = lib.aai_resample_interleaved_device(_ref(request), int(batch), int(channels), src_ptr, int(src_dtype), src_stride,
-                                             src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(lib.aai_resample_interleaved_device(_ref(request), int(batch), int(channels), src_ptr, int(src_dtype), src_stride,
+                                               src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream))
 
 
 def resample_device(request, src_ptr, src_stride, dst_ptr, dst_stride, stream=0, batch=None,
@@ -263,18 +249,13 @@ def resample_device(request, src_ptr, src_stride, dst_ptr, dst_stride, stream=0,
     src_dtype: DTYPE_F32 (default) / DTYPE_U8 / DTYPE_U16 -- strides are in source elements."""
     lib = L.load()
     if src_dtype != L.DTYPE_F32:
-        rc = lib.aai_resample_batch_device(_ref(request), 1 if batch is None else int(batch), src_ptr, int(src_dtype),
-                                           src_stride, src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream)
-        if rc != L.OK:
-            raise AaiError(rc, last_error())
-        return
-    if batch is None:
-        rc = lib.aai_resample_device_f32(_ref(request), src_ptr, src_stride, dst_ptr, dst_stride, stream)
+        _check(lib.aai_resample_batch_device(_ref(request), 1 if batch is None else int(batch), src_ptr, int(src_dtype),
+                                             src_stride, src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream))
+    elif batch is None:
+        _check(lib.aai_resample_device_f32(_ref(request), src_ptr, src_stride, dst_ptr, dst_stride, stream))
     else:
-        rc = lib.aai_resample_batch_device_f32(_ref(request), int(batch), src_ptr, src_stride, src_image_stride,
-                                               dst_ptr, dst_stride, dst_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+        _check(lib.aai_resample_batch_device_f32(_ref(request), int(batch), src_ptr, src_stride, src_image_stride,
+                                                 dst_ptr, dst_stride, dst_image_stride, stream))
 
 
 # (interleaved entry?, planned kind) -> (device entry, host entry).  The interleaved entries have no ("planned") row: the interleaved
@@ -317,31 +298,39 @@ def _adjoint_device(interleaved, planned, request, batch, channels, gdst_ptr, ds
     """the device entry of _ADJOINT_ENTRY (kind: the family, where the caller names it instead of `planned`); the interleaved entries take
     the channel count after the batch"""
     fn = getattr(L.load(), _ADJOINT_ENTRY[interleaved, kind or _planned_kind(planned, interleaved)][0])
-    rc = fn(_ref(request), 1 if batch is None else int(batch), *((int(channels),) if interleaved else ()), gdst_ptr, dst_stride,
-            dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(fn(_ref(request), 1 if batch is None else int(batch), *((int(channels),) if interleaved else ()), gdst_ptr, dst_stride,
+              dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream))
 
 
-def _adjoint_host(interleaved, planned, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, kind=None):
-    """the host entry of _ADJOINT_ENTRY on gdst = [dH, dW] (single-channel) or [dH, dW, C] (interleaved)"""
-    lib = L.load()
+def _adjoint_host(dtype, entry, interleaved, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, name="gdst"):
+    """Every host adjoint entry on gdst = [dH, dW], or (interleaved) [dH, dW] / [dH, dW, C], of `dtype`: entry(request, C, gdst, gdst
+    stride, gsrc, gsrc stride, None) names the C entry and puts C where it takes it -- called last, so that what it raises comes
+    behind a failed query and a gdst of the wrong shape (`name` in that text).  Returns (code, message, gsrc or None)."""
     H, W = int(src_shape[0]), int(src_shape[1])
     rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
     rc, msg, lay = query(rq)
     if rc != L.OK:
         return rc, msg, None
-    g = np.ascontiguousarray(gdst, dtype=np.float32)
+    g = np.ascontiguousarray(gdst, dtype=dtype)
     tail = g.shape[2:] if interleaved else ()                      # () or (C,)
-    C = tail[0] if interleaved else 1
+    C = tail[0] if tail else 1
     if (g.shape[:2] if interleaved else g.shape) != (lay.dst_height, lay.dst_width):
-        raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width) + tail,))
-    gsrc = np.empty((H, W) + tail, dtype=np.float32)
-    fn = getattr(lib, _ADJOINT_ENTRY[interleaved, kind or _planned_kind(planned, interleaved)][1])
-    rc = fn(_ref(rq), *((C,) if interleaved else ()), g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
+        raise ValueError("%s must have the output's shape %r" % (name, (lay.dst_height, lay.dst_width) + tail))
+    gsrc = np.empty((H, W) + tail, dtype=dtype)
+    rc = entry(_ref(rq), C, g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
     if rc != L.OK:
         return rc, last_error(), None
     return rc, "", gsrc
+
+
+def _adjoint_host_f32(interleaved, planned, gdst, *request, kind=None):
+    """the fp32 host entry of _ADJOINT_ENTRY; the interleaved entries take the channel count behind the request"""
+    lib = L.load()
+
+    def entry(rq, C, *images):
+        fn = getattr(lib, _ADJOINT_ENTRY[interleaved, kind or _planned_kind(planned, interleaved)][1])
+        return fn(rq, *((C,) if interleaved else ()), *images)
+    return _adjoint_host(np.float32, entry, interleaved, gdst, *request)
 
 
 def adjoint_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None,
@@ -361,25 +350,21 @@ def adjoint_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0
 def adjoint_prepare(request):
     """aai_adjoint_prepare: aai_prepare plus the adjoint tables of the plan, so that adjoint_device(..., planned=True) only
     enqueues.  A validated no-op for requests the planned adjoint hands to the general kernels."""
-    rc = L.load().aai_adjoint_prepare(_ref(request))
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_adjoint_prepare(_ref(request)))
 
 
 def adjoint_rotated_prepare(request):
     """aai_adjoint_rotated_prepare: aai_prepare plus the plan's adjoint tables at EVERY rotation -- the sums and knife lists of a general
     rotation (8 bytes per dst pixel on the device), the tables of adjoint_prepare at multiples of 90 degrees -- so that
     adjoint_device(..., planned="any") only enqueues."""
-    rc = L.load().aai_adjoint_rotated_prepare(_ref(request))
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_adjoint_rotated_prepare(_ref(request)))
 
 
 def adjoint_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle,
                  mode=L.MODE_AREA, policy=L.POLICY_REFERENCE, planned=False):
     """Host-buffer adjoint (aai_adjoint_f32; planned=True: aai_adjoint_planned_f32; planned="any": aai_adjoint_rotated_f32): gdst is the [dH, dW] gradient with respect to
     the output of resample_host(src of shape src_shape = (H, W), ...); returns (code, message, gsrc [H, W] float32 or None)."""
-    return _adjoint_host(False, planned, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    return _adjoint_host_f32(False, planned, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
 
 
 def adjoint_interleaved_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None,
@@ -410,7 +395,7 @@ def adjoint_interleaved_host(gdst, src_shape, src_resolution, dst_resolution, sr
         raise ValueError("gdst must be a [dH, dW, C] array")
     if len(src_shape) == 3 and int(src_shape[2]) != g.shape[2]:
         raise ValueError("gdst has %d channels, src_shape %d" % (g.shape[2], int(src_shape[2])))
-    return _adjoint_host(True, planned, g, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    return _adjoint_host_f32(True, planned, g, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
 
 
 def adjoint_sample_device(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None, dst_image_stride=0, src_image_stride=0):
@@ -426,7 +411,7 @@ def adjoint_sample_host(gdst, src_shape, src_resolution, dst_resolution, src_iso
     """Host-buffer adjoint of the samplers (aai_adjoint_sample_f32): gdst is the [dH, dW] gradient with respect to the output of
     resample_host(src of shape src_shape = (H, W), ..., mode=MODE_BILINEAR or MODE_BICUBIC); returns (code, message, gsrc [H, W] float32
     or None).  The device entry's bits."""
-    return _adjoint_host(False, False, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, kind="sample")
+    return _adjoint_host_f32(False, False, gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, kind="sample")
 
 
 def adjoint_sample_interleaved_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None, dst_image_stride=0,
@@ -448,7 +433,7 @@ def adjoint_sample_interleaved_host(gdst, src_shape, src_resolution, dst_resolut
         raise ValueError("gdst must be a [dH, dW, C] array")
     if len(src_shape) == 3 and int(src_shape[2]) != g.shape[2]:
         raise ValueError("gdst has %d channels, src_shape %d" % (g.shape[2], int(src_shape[2])))
-    return _adjoint_host(True, False, g, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, kind="sample")
+    return _adjoint_host_f32(True, False, g, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, kind="sample")
 
 
 def resample_device_f64(request, src_ptr, src_stride, dst_ptr, dst_stride, stream=0, batch=None, src_image_stride=0, dst_image_stride=0):
@@ -456,10 +441,8 @@ def resample_device_f64(request, src_ptr, src_stride, dst_ptr, dst_stride, strea
     the reference's own precision.  Raw device pointers (ints), strides in elements (doubles), a hipStream_t handle; every element of
     the output is written.  No plan, nothing to prepare: the call only enqueues, the first call of a geometry included, and can be
     captured.  Single-channel; bilinear / bicubic requests raise AaiError."""
-    rc = L.load().aai_resample_batch_device_f64(_ref(request), 1 if batch is None else int(batch), src_ptr, src_stride, src_image_stride,
-                                                dst_ptr, dst_stride, dst_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_resample_batch_device_f64(_ref(request), 1 if batch is None else int(batch), src_ptr, src_stride, src_image_stride,
+                                                  dst_ptr, dst_stride, dst_image_stride, stream))
 
 
 def adjoint_device_f64(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stream=0, batch=None, dst_image_stride=0, src_image_stride=0):
@@ -467,10 +450,8 @@ def adjoint_device_f64(request, gdst_ptr, dst_stride, gsrc_ptr, src_stride, stre
     what resample_device_f64 computes, pair by pair with the same weight bits; adjoint_device's two passes without its final fp32
     rounding.  Raw device pointers (ints), strides in elements (doubles), a hipStream_t handle; every element of the src_width x
     src_height gradient image is written.  No plan: the call only enqueues and can be captured."""
-    rc = L.load().aai_adjoint_batch_device_f64(_ref(request), 1 if batch is None else int(batch), gdst_ptr, dst_stride, dst_image_stride,
-                                               gsrc_ptr, src_stride, src_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_adjoint_batch_device_f64(_ref(request), 1 if batch is None else int(batch), gdst_ptr, dst_stride, dst_image_stride,
+                                                 gsrc_ptr, src_stride, src_image_stride, stream))
 
 
 def resample_exact_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
@@ -486,17 +467,7 @@ def resample_exact_host(src, src_resolution, dst_resolution, src_isocenter, rota
             raise ValueError("src must be a 2-D image [H, W]")
         a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
     a = np.ascontiguousarray(a, dtype=np.float64)
-    H, W = a.shape
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None, None, None
-    dst = np.empty((lay.dst_height, lay.dst_width), dtype=np.float64)
-    out_lay = L.Layout()
-    rc = lib.aai_resample_exact_f64(_ref(rq), a.ctypes.data, W, dst.ctypes.data, max(lay.dst_width, 1), ctypes.byref(out_lay))
-    if rc != L.OK:
-        return rc, last_error(), None, None, None
-    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+    return _host_forward(a, 1, False, (src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy), lib.aai_resample_exact_f64)
 
 
 def adjoint_exact_host(gdst, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
@@ -504,19 +475,8 @@ def adjoint_exact_host(gdst, src_shape, src_resolution, dst_resolution, src_isoc
     resample_exact_host(src of shape src_shape = (H, W), ...); returns (code, message, gsrc [H, W] float64 or None).  The bits of
     adjoint_device_f64."""
     lib = L.load()
-    H, W = int(src_shape[0]), int(src_shape[1])
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None
-    g = np.ascontiguousarray(gdst, dtype=np.float64)
-    if g.shape != (lay.dst_height, lay.dst_width):
-        raise ValueError("gdst must have the output's shape %r" % ((lay.dst_height, lay.dst_width),))
-    gsrc = np.empty((H, W), dtype=np.float64)
-    rc = lib.aai_adjoint_f64(_ref(rq), g.ctypes.data, max(lay.dst_width, 1), gsrc.ctypes.data, max(W, 1), None)
-    if rc != L.OK:
-        return rc, last_error(), None
-    return rc, "", gsrc
+    return _adjoint_host(np.float64, lambda rq, C, *images: lib.aai_adjoint_f64(rq, *images), False, gdst, src_shape, src_resolution, dst_resolution,
+                         src_isocenter, rotation_angle, mode, policy)
 
 
 def resample_half_device(request, src_ptr, src_stride, dst_ptr, dst_stride, half_dtype, stream=0, batch=None, src_image_stride=0, dst_image_stride=0):
@@ -526,10 +486,8 @@ def resample_half_device(request, src_ptr, src_stride, dst_ptr, dst_stride, half
     modes.  The plan is resample_device's (prepare(request, 1) prepares this call too); rotations by 0 / 180 degrees in the area / fast
     modes run one streaming kernel on the half images (last_kernel(): "aai_axis_half_kernel<f16>" / "<bf16>"), everything else widens
     into fp32 scratch, runs resample_device's launches and narrows ("<fp32 kernel>+widened")."""
-    rc = L.load().aai_resample_half_batch_device(_ref(request), 1 if batch is None else int(batch), int(half_dtype), src_ptr, src_stride, src_image_stride,
-                                                 dst_ptr, dst_stride, dst_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_resample_half_batch_device(_ref(request), 1 if batch is None else int(batch), int(half_dtype), src_ptr, src_stride, src_image_stride,
+                                                   dst_ptr, dst_stride, dst_image_stride, stream))
 
 
 def resample_half_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE, half_dtype=None):
@@ -549,17 +507,7 @@ def resample_half_host(src, src_resolution, dst_resolution, src_isocenter, rotat
             raise ValueError("src must be a 2-D image [H, W]")
         a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
     a = np.ascontiguousarray(a)
-    H, W = a.shape
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None, None, None
-    dst = np.empty((lay.dst_height, lay.dst_width), dtype=a.dtype)
-    out_lay = L.Layout()
-    rc = lib.aai_resample_half_host(_ref(rq), int(half_dtype), a.ctypes.data, max(W, 1), dst.ctypes.data, max(lay.dst_width, 1), ctypes.byref(out_lay))
-    if rc != L.OK:
-        return rc, last_error(), None, None, None
-    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+    return _host_forward(a, 1, False, (src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy), lib.aai_resample_half_host, int(half_dtype))
 
 
 def resample_half_interleaved_device(request, channels, src_ptr, src_stride, dst_ptr, dst_stride, half_dtype, stream=0, batch=None, src_image_stride=0,
@@ -570,10 +518,8 @@ def resample_half_interleaved_device(request, channels, src_ptr, src_stride, dst
     hipStream_t handle.  The plan is resample_interleaved_device's (prepare(request, channels) prepares this call too); rotations by
     0 / 180 degrees in the area / fast modes run one streaming kernel (last_kernel(): "aai_axis_half_kernel<f16>" / "<bf16>"),
     everything else widens into fp32 scratch, runs resample_interleaved_device's launches and narrows ("<fp32 kernel>+widened")."""
-    rc = L.load().aai_resample_half_interleaved_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(half_dtype), src_ptr, src_stride,
-                                                       src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_resample_half_interleaved_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(half_dtype), src_ptr, src_stride,
+                                                         src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream))
 
 
 def resample_half_interleaved_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
@@ -595,19 +541,9 @@ def resample_half_interleaved_host(src, src_resolution, dst_resolution, src_isoc
             raise ValueError("src must be an image [H, W] or [H, W, C]")
         a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
     a = np.ascontiguousarray(a)
-    H, W = a.shape[:2]
     C = a.shape[2] if a.ndim == 3 else 1
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None, None, None
-    dst = np.empty((lay.dst_height, lay.dst_width) + ((C,) if a.ndim == 3 else ()), dtype=a.dtype)
-    out_lay = L.Layout()
-    rc = lib.aai_resample_half_interleaved_host(_ref(rq), C, int(half_dtype), a.ctypes.data, max(W * C, 1), dst.ctypes.data, max(lay.dst_width * C, 1),
-                                                ctypes.byref(out_lay))
-    if rc != L.OK:
-        return rc, last_error(), None, None, None
-    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+    return _host_forward(a, C, a.ndim == 3, (src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy),
+                         lib.aai_resample_half_interleaved_host, C, int(half_dtype))
 
 
 def adjoint_half_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr, src_stride, half_dtype, stream=0, batch=None, dst_image_stride=0,
@@ -619,10 +555,8 @@ def adjoint_half_device(request, channels, gdst_ptr, dst_stride, gsrc_ptr, src_s
     planned="separable"): at rotations by multiples of 90 degrees on a plan without correction lists ONE launch on the half images
     (last_kernel(): "aai_axis_adjoint_half_kernel<f16|bf16,C>"), everything else widens into fp32 scratch, runs that entry's launches
     and narrows ("<fp32 route>+widened").  adjoint_rotated_prepare(request) prepares these calls."""
-    rc = L.load().aai_adjoint_half_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(half_dtype), gdst_ptr, dst_stride,
-                                          dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_adjoint_half_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(half_dtype), gdst_ptr, dst_stride,
+                                            dst_image_stride, gsrc_ptr, src_stride, src_image_stride, stream))
 
 
 def adjoint_half_host(gdst_bits, src_shape, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
@@ -638,21 +572,8 @@ def adjoint_half_host(gdst_bits, src_shape, src_resolution, dst_resolution, src_
         raise TypeError("adjoint_half_host takes np.uint16 images of raw fp16 / bf16 bits, got %s" % g.dtype)
     if g.ndim not in (2, 3):
         raise ValueError("gdst_bits must be a [dH, dW] or [dH, dW, C] array")
-    g = np.ascontiguousarray(g)
-    H, W = int(src_shape[0]), int(src_shape[1])
-    tail = g.shape[2:]
-    C = tail[0] if tail else 1
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None
-    if g.shape[:2] != (lay.dst_height, lay.dst_width):
-        raise ValueError("gdst_bits must have the output's shape %r" % ((lay.dst_height, lay.dst_width) + tail,))
-    gsrc = np.empty((H, W) + tail, dtype=np.uint16)
-    rc = lib.aai_adjoint_half_host(_ref(rq), C, int(half_dtype), g.ctypes.data, max(lay.dst_width * C, 1), gsrc.ctypes.data, max(W * C, 1), None)
-    if rc != L.OK:
-        return rc, last_error(), None
-    return rc, "", gsrc
+    return _adjoint_host(np.uint16, lambda rq, C, *images: lib.aai_adjoint_half_host(rq, C, int(half_dtype), *images), True, g, src_shape, src_resolution,
+                         dst_resolution, src_isocenter, rotation_angle, mode, policy, name="gdst_bits")
 
 
 def resample_int_device(request, channels, src_ptr, src_stride, dst_ptr, dst_stride, dtype, stream=0, batch=None, src_image_stride=0, dst_image_stride=0):
@@ -663,10 +584,8 @@ def resample_int_device(request, channels, src_ptr, src_stride, dst_ptr, dst_str
     channels) prepares this call too); rotations by 0 / 180 degrees in the area / fast modes run one streaming kernel on the integer
     images (last_kernel(): "aai_axis_int_kernel<u8>" / "<u16>"), everything else runs resample_interleaved_device's launches into fp32
     scratch and converts ("<fp32 kernel>+quantized")."""
-    rc = L.load().aai_resample_int_batch_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(dtype), src_ptr, src_stride,
-                                                src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_resample_int_batch_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(dtype), src_ptr, src_stride,
+                                                  src_image_stride, dst_ptr, dst_stride, dst_image_stride, stream))
 
 
 def resample_int_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE):
@@ -684,18 +603,8 @@ def resample_int_host(src, src_resolution, dst_resolution, src_isocenter, rotati
             raise ValueError("src must be an image [H, W] or [H, W, C]")
         a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
     a = np.ascontiguousarray(a)
-    H, W = a.shape[:2]
     C = a.shape[2] if a.ndim == 3 else 1
-    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
-    rc, msg, lay = query(rq)
-    if rc != L.OK:
-        return rc, msg, None, None, None
-    dst = np.empty((lay.dst_height, lay.dst_width) + ((C,) if a.ndim == 3 else ()), dtype=a.dtype)
-    out_lay = L.Layout()
-    rc = lib.aai_resample_int_host(_ref(rq), C, dtype, a.ctypes.data, max(W * C, 1), dst.ctypes.data, max(lay.dst_width * C, 1), ctypes.byref(out_lay))
-    if rc != L.OK:
-        return rc, last_error(), None, None, None
-    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+    return _host_forward(a, C, a.ndim == 3, (src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy), lib.aai_resample_int_host, C, dtype)
 
 
 def resample_multi_device(request, shards, src_stride, src_image_stride, dst_stride, dst_image_stride):
@@ -707,27 +616,21 @@ def resample_multi_device(request, shards, src_stride, src_image_stride, dst_str
     srcs = (ctypes.c_void_p * n)(*[s[2] for s in shards])
     dsts = (ctypes.c_void_p * n)(*[s[3] for s in shards])
     strs = (ctypes.c_void_p * n)(*[s[4] for s in shards])
-    rc = L.load().aai_resample_batch_multi_device_f32(_ref(request), n, devs, cnts, srcs, src_stride, src_image_stride,
-                                                     dsts, dst_stride, dst_image_stride, strs)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_resample_batch_multi_device_f32(_ref(request), n, devs, cnts, srcs, src_stride, src_image_stride,
+                                                       dsts, dst_stride, dst_image_stride, strs))
 
 
 def band_source_rows(request, dst_row0, dst_row1):
     """aai_band_source_rows: source rows [a, b) that dst rows [dst_row0, dst_row1) read.  Needs no GPU."""
     a, b = ctypes.c_int32(), ctypes.c_int32()
-    rc = L.load().aai_band_source_rows(_ref(request), int(dst_row0), int(dst_row1), ctypes.byref(a), ctypes.byref(b))
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_band_source_rows(_ref(request), int(dst_row0), int(dst_row1), ctypes.byref(a), ctypes.byref(b)))
     return a.value, b.value
 
 
 def resample_band_device(request, dst_row0, dst_row1, src_rows_ptr, src_stride, dst_rows_ptr, dst_stride, stream=0):
     """aai_resample_band_device_f32: src_rows_ptr addresses source row band_source_rows(...)[0], dst_rows_ptr output row dst_row0."""
-    rc = L.load().aai_resample_band_device_f32(_ref(request), int(dst_row0), int(dst_row1), src_rows_ptr, src_stride,
-                                               dst_rows_ptr, dst_stride, stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_resample_band_device_f32(_ref(request), int(dst_row0), int(dst_row1), src_rows_ptr, src_stride,
+                                                 dst_rows_ptr, dst_stride, stream))
 
 
 def plan_shape(request, channels=1):
@@ -735,9 +638,7 @@ def plan_shape(request, channels=1):
     kernel family, K1 launch shape and its origin, flagged pixels, fp32 formulation, build time, adjoint tables (tables | none), and last the tables of the planned adjoint at general rotations
     (rot_adjoint=none | sums | general, then knife=<count> once its scan has run)."""
     buf = ctypes.create_string_buffer(512)
-    rc = L.load().aai_plan_info(_ref(request), int(channels), buf, 512)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_plan_info(_ref(request), int(channels), buf, 512))
     return buf.value.decode()
 
 
@@ -763,22 +664,16 @@ def shutdown():
 def prepare(request, channels=1):
     """aai_prepare: build (and cache) the plan of this request on the current device now -- K1 tables, the one-off
     scans of a rotated geometry -- instead of inside the first resampling call, which would then synchronise."""
-    rc = L.load().aai_prepare(_ref(request), int(channels))
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_prepare(_ref(request), int(channels)))
 
 
 def synth_rows_device(dst_ptr, width, height, row0, row1, stride, seed, stream=0):
     """rows [row0, row1) of the synthetic width x height image; dst_ptr addresses row row0"""
-    rc = L.load().aai_synth_rows_device_f32(dst_ptr, int(width), int(height), int(row0), int(row1), int(stride), int(seed), stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_synth_rows_device_f32(dst_ptr, int(width), int(height), int(row0), int(row1), int(stride), int(seed), stream))
 
 
 def synth_device(dst_ptr, width, height, stride, seed, stream=0):
-    rc = L.load().aai_synth_device_f32(dst_ptr, int(width), int(height), int(stride), int(seed), stream)
-    if rc != L.OK:
-        raise AaiError(rc, last_error())
+    _check(L.load().aai_synth_device_f32(dst_ptr, int(width), int(height), int(stride), int(seed), stream))
 
 
 class AreaAverageInterpolation:

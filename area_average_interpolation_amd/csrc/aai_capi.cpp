@@ -59,6 +59,18 @@ int check_dtype(int32_t dtype)
     return AAI_OK;
 }
 
+int check_half_dtype(int32_t dtype)      // include/aai_half.h, aai_half_interleaved.h, aai_adjoint_half.h
+{
+    if (dtype != AAI_HALF_F16 && dtype != AAI_HALF_BF16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown half-precision element type.");
+    return AAI_OK;
+}
+
+int check_int_dtype(int32_t dtype)      // include/aai_int.h
+{
+    if (dtype != AAI_DTYPE_U8 && dtype != AAI_DTYPE_U16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown integer element type.");
+    return AAI_OK;
+}
+
 int check_channels(int32_t channels)
 {
     return channels < 1 || channels > 4 ? fail(AAI_ERR_BAD_ARGUMENT, "Channels must be 1..4.") : AAI_OK;
@@ -90,15 +102,17 @@ int check_strides(const aai::Geometry &g, int channels, int64_t srcStride, int64
 }
 
 // The adjoint of an area / fast request: the argument checks of every adjoint entry, none of which needs a device -- the request's
-// part (all aai_adjoint_prepare has to check) ...
-int check_adjoint_request(const aai_request *rq, int batch, aai::Geometry &g)
+// part (all aai_adjoint_prepare has to check) ...  `subject` names the caller in the texts: the forward of include/aai_f64.h takes
+// the same modes and runs the same checks (check_f64_forward).
+int check_adjoint_request(const aai_request *rq, int batch, aai::Geometry &g, const char *subject = "adjoint")
 {
     AAI_TRY(check_request(rq));
     AAI_TRY(check_batch(batch));
     AAI_TRY(request_geometry(*rq, g));
-    if (rq->mode == AAI_MODE_BILINEAR) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BILINEAR: the area and fast modes only.");
-    if (rq->mode == AAI_MODE_BICUBIC) return fail(AAI_ERR_BAD_ARGUMENT, "No adjoint for AAI_MODE_BICUBIC: the area and fast modes only.");
-    if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the adjoint.");
+    const std::string no = std::string("No ") + subject + " for ";
+    if (rq->mode == AAI_MODE_BILINEAR) return fail(AAI_ERR_BAD_ARGUMENT, no + "AAI_MODE_BILINEAR: the area and fast modes only.");
+    if (rq->mode == AAI_MODE_BICUBIC) return fail(AAI_ERR_BAD_ARGUMENT, no + "AAI_MODE_BICUBIC: the area and fast modes only.");
+    if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, std::string("AAI_POLICY_DIAG_NO_FIXUP has no meaning for the ") + subject + ".");
     return AAI_OK;
 }
 // Its sibling for the samplers' adjoint (include/aai_adjoint_sample.h): ONLY the bilinear and bicubic modes.  The policy's rule and bits are
@@ -115,10 +129,10 @@ int check_adjoint_sample_request(const aai_request *rq, int batch, aai::Geometry
 // ... and the images'.  The interleaved entries (aai_adjoint_interleaved_*, aai_adjoint_rotated_interleaved_*, aai_adjoint_planned_interleaved_*) check the channel count
 // right after the request, as the forward's interleaved entries report it, and the row length before the pointers; the single-channel
 // entries check neither.  Strides in elements of `channels` per pixel.
-int check_half_dtype(int32_t dtype);
-// (halfDtype: the element type of the entries of include/aai_adjoint_half.h, checked directly behind the channel count; the fp32 entries pass none)
-int check_adjoint(AdjointFamily family, const aai_request *rq, int batch, bool interleaved, int channels, const void *gdst, int64_t dstStride,
-                  const void *gsrc, int64_t srcStride, aai::Geometry &g, const int32_t *halfDtype = nullptr)
+// (halfDtype: the element type of the entries of include/aai_adjoint_half.h, checked directly behind the channel count; NULL: the fp32 and
+// f64 entries, which have none)
+int check_adjoint(AdjointFamily family, const aai_request *rq, int batch, bool interleaved, int channels, const int32_t *halfDtype, const void *gdst,
+                  int64_t dstStride, const void *gsrc, int64_t srcStride, aai::Geometry &g)
 {
     if (interleaved) {
         AAI_TRY(check_request(rq));
@@ -131,17 +145,48 @@ int check_adjoint(AdjointFamily family, const aai_request *rq, int batch, bool i
     return check_strides(g, channels, srcStride, dstStride);
 }
 
+// The forward of the reference-precision path (include/aai_f64.h): the checks of a single-channel general adjoint, check for check, in
+// its order and with its messages where they apply (the adjoint entries of aai_f64.h run check_adjoint itself).
+int check_f64_forward(const aai_request *rq, int batch, const void *src, int64_t srcStride, const void *dst, int64_t dstStride, aai::Geometry &g)
+{
+    AAI_TRY(check_adjoint_request(rq, batch, g, "f64 forward"));
+    AAI_TRY(check_pointers(src, dst));
+    return check_strides(g, 1, srcStride, dstStride);
+}
+
+// ---- the tail of a device entry ----------------------------------------------------------------------------------------------
+// The argument checks done: (an empty batch is done, without a look at the device;) the device check; `late`, a check the entry
+// reports from behind the device check; `run`, its enqueue; a clean error text.  Two variations live in the arguments and are pinned
+// by the recordings of tests/test_entry_point_errors.py ("The entry layer"):
+//   emptyBatch  `batch == 0` from the entries that have the shortcut, `false` from those that do not: the fp32 forward entries, whose
+//               empty batch goes on to the device check and into enqueue()
+//   late        the strides of the half / integer device entries, which stand where the fp32 forward entries report theirs: in enqueue()
+template <typename Late, typename Run>
+int device_tail(bool emptyBatch, Late late, Run run)
+{
+    if (!emptyBatch) {
+        AAI_TRY(require_device());
+        AAI_TRY(late());
+        AAI_TRY(run());
+    }
+    g_lastError.clear();
+    return AAI_OK;
+}
+template <typename Run>
+int device_tail(bool emptyBatch, Run run)
+{
+    return device_tail(emptyBatch, [] { return (int)AAI_OK; }, run);
+}
+
 // every device entry of the adjoint; the single-channel entries pass interleaved = false, channels = 1
 int adjoint_device(AdjointFamily family, bool interleaved, const aai_request *req, int32_t batch, int32_t channels, const float *d_gdst,
                    int64_t dst_stride, int64_t dst_image_stride, float *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(family, req, batch, interleaved, channels, d_gdst, dst_stride, d_gsrc, src_stride, g));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue_adjoint(family, *req, g, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    AAI_TRY(check_adjoint(family, req, batch, interleaved, channels, nullptr, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    return device_tail(batch == 0, [&] {
+        return enqueue_adjoint(family, *req, g, batch, channels, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream);
+    });
 }
 
 // aai_adjoint_prepare / aai_adjoint_rotated_prepare
@@ -149,10 +194,7 @@ int adjoint_prepare(AdjointFamily family, const aai_request *req)
 {
     aai::Geometry g;
     AAI_TRY(check_adjoint_request(req, 1, g));
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue_adjoint(family, *req, g, 0, 1, nullptr, 0, 0, nullptr, 0, 0, nullptr));
-    g_lastError.clear();
-    return AAI_OK;
+    return device_tail(false, [&] { return enqueue_adjoint(family, *req, g, 0, 1, nullptr, 0, 0, nullptr, 0, 0, nullptr); });
 }
 
 int finish(const aai_request &rq, const aai::Geometry &g, aai_layout *layout)
@@ -174,42 +216,76 @@ struct DeviceBuffer {
     template <typename T> T *as() const { return static_cast<T *>(p); }
 };
 
-// dense device rows <-> strided host rows; sizes in elements of `esz` bytes
-hipError_t upload(const DeviceBuffer &d, const void *h, int64_t hStride, int64_t row, int rows, size_t esz)
+// One image of a host round trip: the caller's strided rows and the dense rows of their twin on the device.  Sizes in elements of
+// `esz` bytes.  (src_image / dst_image: the request's source and output with `channels` interleaved elements per pixel.  An adjoint
+// reads a dst_image, gdst, and writes a src_image, gsrc.)
+struct HostImage {
+    void *p;
+    int64_t stride, row;
+    int rows;
+    size_t esz;
+    size_t bytes() const { return esz * (size_t)row * (size_t)rows; }
+};
+HostImage src_image(const aai::Geometry &g, int channels, const void *p, int64_t stride, size_t esz)
 {
-    return hipMemcpy2D(d.p, esz * row, h, esz * hStride, esz * row, rows, hipMemcpyHostToDevice);
+    return {const_cast<void *>(p), stride, (int64_t)g.W * channels, g.H, esz};
 }
-hipError_t download(void *h, int64_t hStride, const DeviceBuffer &d, int64_t row, int rows, size_t esz)
+HostImage dst_image(const aai::Geometry &g, int channels, const void *p, int64_t stride, size_t esz)
 {
-    return hipMemcpy2D(h, esz * hStride, d.p, esz * row, esz * row, rows, hipMemcpyDeviceToHost);
+    return {const_cast<void *>(p), stride, (int64_t)g.dW * channels, g.dH, esz};
 }
 
-// The host round trip behind aai_resample_f32 / _f64 / _host / _interleaved_host, the caller's checks done: upload, one launch on
-// the null stream, download.  srcType: AAI_DTYPE_* of the host source; f64: host source AND destination are doubles instead,
-// converted to and from fp32 on the device.  Strides in elements.
+// THE host round trip, behind every host entry but the pipelined aai_resample_batch_host, the caller's checks done: two dense device
+// images, `in` uploaded, run(dIn, dOut, stream) -> int enqueues once on the null stream, synchronise, `out` downloaded, finish().
+// launchWhenEmpty says what an output without elements means ("The entry layer", has the table): true = nothing is
+// skipped (the adjoint entries); false = the input still goes up, and the output's allocation, run(), the wait and the download are
+// skipped (the fp32 forward entries).  An entry that returns before it touches the allocator says so itself, in front of this call.
+template <typename Run>
+int round_trip(const aai_request &rq, const aai::Geometry &g, const HostImage &in, const HostImage &out, bool launchWhenEmpty, aai_layout *layout, Run run)
+{
+    const bool launch = launchWhenEmpty || out.bytes() != 0;
+    DeviceBuffer dIn, dOut;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dIn.alloc(in.bytes()));
+    if (launch) AAI_HIP(dOut.alloc(out.bytes()));
+    AAI_HIP(hipMemcpy2D(dIn.p, in.esz * in.row, in.p, in.esz * in.stride, in.esz * in.row, in.rows, hipMemcpyHostToDevice));
+    if (launch) {
+        AAI_TRY(run(dIn.p, dOut.p, stream));
+        AAI_HIP(hipStreamSynchronize(stream));
+        AAI_HIP(hipMemcpy2D(out.p, out.esz * out.stride, dOut.p, out.esz * out.row, out.esz * out.row, out.rows, hipMemcpyDeviceToHost));
+    }
+    return finish(rq, g, layout);
+}
+
+// aai_resample_f32 / _f64 / _host / _interleaved_host.  srcType: AAI_DTYPE_* of the host source; f64: host source AND destination are
+// doubles instead, converted to and from fp32 on the device.  Strides in elements.
 int host_round_trip(const aai_request &rq, const aai::Geometry &g, int channels, int srcType, bool f64, const void *src, int64_t srcStride,
                     void *dst, int64_t dstStride, aai_layout *layout)
 {
-    const int64_t rowIn = (int64_t)g.W * channels, rowOut = (int64_t)g.dW * channels;      // elements per dense row
-    const size_t nSrc = (size_t)rowIn * g.H, nDst = (size_t)rowOut * g.dH;
-    const size_t inSize = f64 ? sizeof(double) : aai::src_elem_size(srcType), outSize = f64 ? sizeof(double) : sizeof(float);
-    hipStream_t stream = nullptr;
-    DeviceBuffer in, out, in32, out64;      // in32 / out64: the fp32 source and the fp64 result of a double-precision call
-    AAI_HIP(in.alloc(inSize * nSrc));
-    AAI_HIP(upload(in, src, srcStride, rowIn, g.H, inSize));
-    if (nDst) AAI_HIP(out.alloc(sizeof(float) * nDst));
-    if (f64) {
+    const HostImage in = src_image(g, channels, src, srcStride, f64 ? sizeof(double) : aai::src_elem_size(srcType));
+    const HostImage out = dst_image(g, channels, dst, dstStride, f64 ? sizeof(double) : sizeof(float));
+    const size_t nSrc = (size_t)in.row * g.H, nDst = (size_t)out.row * g.dH;
+    DeviceBuffer in32, out32;      // the fp32 source and result of a double-precision call (freed behind the round trip's wait)
+    return round_trip(rq, g, in, out, /*launchWhenEmpty*/ false, layout, [&](const void *dIn, void *dOut, hipStream_t stream) -> int {
+        if (!f64) return enqueue(rq, g, 1, dIn, srcType, in.row, 0, static_cast<float *>(dOut), out.row, 0, stream, -1, -1, channels);
         AAI_HIP(in32.alloc(sizeof(float) * nSrc));
-        AAI_HIP(aai::launch_f64_to_f32(in.as<const double>(), in32.as<float>(), nSrc, stream));
-        if (nDst) AAI_HIP(out64.alloc(sizeof(double) * nDst));
-    }
-    if (nDst) {
-        AAI_TRY(enqueue(rq, g, 1, f64 ? in32.p : in.p, f64 ? (int)aai::SRC_F32 : srcType, rowIn, 0, out.as<float>(), rowOut, 0, stream, -1, -1, channels));
-        if (f64) AAI_HIP(aai::launch_f32_to_f64(out.as<const float>(), out64.as<double>(), nDst, stream));
-        AAI_HIP(hipStreamSynchronize(stream));
-        AAI_HIP(download(dst, dstStride, f64 ? out64 : out, rowOut, g.dH, outSize));
-    }
-    return finish(rq, g, layout);
+        AAI_HIP(out32.alloc(sizeof(float) * nDst));
+        AAI_HIP(aai::launch_f64_to_f32(static_cast<const double *>(dIn), in32.as<float>(), nSrc, stream));
+        AAI_TRY(enqueue(rq, g, 1, in32.p, aai::SRC_F32, in.row, 0, out32.as<float>(), out.row, 0, stream, -1, -1, channels));
+        AAI_HIP(aai::launch_f32_to_f64(out32.as<const float>(), static_cast<double *>(dOut), nDst, stream));
+        return AAI_OK;
+    });
+}
+
+// aai_resample_half_host / _half_interleaved_host / _int_host: the element type in, the same type out; an output without elements
+// returns before the allocator is touched
+template <typename Run>
+int narrow_round_trip(const aai_request &rq, const aai::Geometry &g, int channels, size_t esz, const void *src, int64_t srcStride, void *dst, int64_t dstStride,
+                      aai_layout *layout, Run run)
+{
+    const HostImage in = src_image(g, channels, src, srcStride, esz), out = dst_image(g, channels, dst, dstStride, esz);
+    if (!out.bytes()) return finish(rq, g, layout);
+    return round_trip(rq, g, in, out, true, layout, run);
 }
 
 // aai_resample_f32 / aai_resample_f64
@@ -292,53 +368,17 @@ bool is_page_locked(const void *p)
     return attr.type == hipMemoryTypeHost;
 }
 
-// every host entry of the adjoint: upload gdst, one launch on the null stream, download gsrc (dense rows of width x channels elements on
-// the device); the single-channel entries pass interleaved = false, channels = 1
+// every fp32 host entry of the adjoint: gdst up, one launch, gsrc down; the single-channel entries pass interleaved = false, channels = 1
 int adjoint_host(AdjointFamily family, bool interleaved, const aai_request *req, int channels, const float *gdst, int64_t dst_stride, float *gsrc,
                  int64_t src_stride, aai_layout *layout)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(family, req, 1, interleaved, channels, gdst, dst_stride, gsrc, src_stride, g));
+    AAI_TRY(check_adjoint(family, req, 1, interleaved, channels, nullptr, gdst, dst_stride, gsrc, src_stride, g));
     AAI_TRY(require_device());
-    const int64_t rowDst = (int64_t)g.dW * channels, rowSrc = (int64_t)g.W * channels;
-    DeviceBuffer dGdst, dGsrc;
-    hipStream_t stream = nullptr;
-    AAI_HIP(dGdst.alloc(sizeof(float) * (size_t)rowDst * g.dH));
-    AAI_HIP(dGsrc.alloc(sizeof(float) * (size_t)rowSrc * g.H));
-    AAI_HIP(upload(dGdst, gdst, dst_stride, rowDst, g.dH, sizeof(float)));
-    AAI_TRY(enqueue_adjoint(family, *req, g, 1, channels, dGdst.as<const float>(), rowDst, 0, dGsrc.as<float>(), rowSrc, 0, stream));
-    AAI_HIP(hipStreamSynchronize(stream));
-    AAI_HIP(download(gsrc, src_stride, dGsrc, rowSrc, g.H, sizeof(float)));
-    return finish(*req, g, layout);
-}
-
-// ---- the reference-precision path (include/aai_f64.h) ----------------------------------------------------------------------
-// The forward's argument checks: those of check_adjoint for a single-channel general adjoint, check for check, in its order and with
-// its messages where they apply (the adjoint entries of aai_f64.h run check_adjoint itself).
-int check_f64_forward(const aai_request *rq, int batch, const void *src, int64_t srcStride, const void *dst, int64_t dstStride, aai::Geometry &g)
-{
-    AAI_TRY(check_request(rq));
-    AAI_TRY(check_batch(batch));
-    AAI_TRY(request_geometry(*rq, g));
-    if (rq->mode == AAI_MODE_BILINEAR) return fail(AAI_ERR_BAD_ARGUMENT, "No f64 forward for AAI_MODE_BILINEAR: the area and fast modes only.");
-    if (rq->mode == AAI_MODE_BICUBIC) return fail(AAI_ERR_BAD_ARGUMENT, "No f64 forward for AAI_MODE_BICUBIC: the area and fast modes only.");
-    if (rq->policy & AAI_POLICY_DIAG_NO_FIXUP) return fail(AAI_ERR_BAD_ARGUMENT, "AAI_POLICY_DIAG_NO_FIXUP has no meaning for the f64 forward.");
-    AAI_TRY(check_pointers(src, dst));
-    return check_strides(g, 1, srcStride, dstStride);
-}
-
-// ---- the half-precision path (include/aai_half.h) --------------------------------------------------------------------------
-int check_half_dtype(int32_t dtype)
-{
-    if (dtype != AAI_HALF_F16 && dtype != AAI_HALF_BF16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown half-precision element type.");
-    return AAI_OK;
-}
-
-// ---- the integer path (include/aai_int.h) ------------------------------------------------------------------------------------
-int check_int_dtype(int32_t dtype)
-{
-    if (dtype != AAI_DTYPE_U8 && dtype != AAI_DTYPE_U16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown integer element type.");
-    return AAI_OK;
+    const HostImage in = dst_image(g, channels, gdst, dst_stride, sizeof(float)), out = src_image(g, channels, gsrc, src_stride, sizeof(float));
+    return round_trip(*req, g, in, out, /*launchWhenEmpty*/ true, layout, [&](const void *dGdst, void *dGsrc, hipStream_t stream) {
+        return enqueue_adjoint(family, *req, g, 1, channels, static_cast<const float *>(dGdst), in.row, 0, static_cast<float *>(dGsrc), out.row, 0, stream);
+    });
 }
 
 }  // namespace
@@ -412,10 +452,9 @@ int aai_resample_batch_device(const aai_request *req, int32_t batch, const void 
     AAI_TRY(check_batch(batch));
     AAI_TRY(request_geometry(*req, g));
     AAI_TRY(check_pointers(d_src, d_dst));
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue(*req, g, batch, d_src, src_dtype, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    return device_tail(false, [&] {
+        return enqueue(*req, g, batch, d_src, src_dtype, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream);
+    });
 }
 
 int aai_resample_batch_device_f32(const aai_request *req, int32_t batch,
@@ -471,10 +510,9 @@ int aai_resample_band_device_f32(const aai_request *req, int32_t dst_row0, int32
     int32_t a, b;
     AAI_TRY(band_source_rows(req, dst_row0, dst_row1, &a, &b, g));
     AAI_TRY(check_pointers(d_src_rows, d_dst_rows));
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue(*req, g, 1, d_src_rows, aai::SRC_F32, src_stride, 0, d_dst_rows, dst_stride, 0, (hipStream_t)stream, dst_row0, dst_row1));
-    g_lastError.clear();
-    return AAI_OK;
+    return device_tail(false, [&] {
+        return enqueue(*req, g, 1, d_src_rows, aai::SRC_F32, src_stride, 0, d_dst_rows, dst_stride, 0, (hipStream_t)stream, dst_row0, dst_row1);
+    });
 }
 
 int aai_prepare(const aai_request *req, int32_t channels)
@@ -483,12 +521,11 @@ int aai_prepare(const aai_request *req, int32_t channels)
     AAI_TRY(check_request(req));
     AAI_TRY(check_channels(channels));
     AAI_TRY(request_geometry(*req, g));
-    AAI_TRY(require_device());
-    PlanRef p;
-    // (the plan of a packed fp32 image: what the device entries build on their first call)
-    AAI_TRY(acquire_plan(*req, g, -1, -1, channels, rot_form(*req, g, channels, aai::SRC_F32, (int64_t)g.W * channels), &p));
-    g_lastError.clear();
-    return AAI_OK;
+    return device_tail(false, [&] {
+        PlanRef p;
+        // (the plan of a packed fp32 image: what the device entries build on their first call)
+        return acquire_plan(*req, g, -1, -1, channels, rot_form(*req, g, channels, aai::SRC_F32, (int64_t)g.W * channels), &p);
+    });
 }
 
 int aai_plan_info(const aai_request *req, int32_t channels, char *text, int32_t capacity)
@@ -526,11 +563,9 @@ int aai_resample_batch_device_f64(const aai_request *req, int32_t batch, const d
 {
     aai::Geometry g;
     AAI_TRY(check_f64_forward(req, batch, d_src, src_stride, d_dst, dst_stride, g));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue_f64_forward(*req, g, batch, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    return device_tail(batch == 0, [&] {
+        return enqueue_f64_forward(*req, g, batch, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream);
+    });
 }
 
 int aai_resample_exact_f64(const aai_request *req, const double *src, int64_t src_stride, double *dst, int64_t dst_stride, aai_layout *layout)
@@ -538,45 +573,32 @@ int aai_resample_exact_f64(const aai_request *req, const double *src, int64_t sr
     aai::Geometry g;
     AAI_TRY(check_f64_forward(req, 1, src, src_stride, dst, dst_stride, g));
     AAI_TRY(require_device());
-    const size_t nSrc = (size_t)g.W * g.H, nDst = (size_t)g.dW * g.dH;
-    if (!nDst) return finish(*req, g, layout);
-    DeviceBuffer dSrc, dDst;
-    hipStream_t stream = nullptr;
-    AAI_HIP(dSrc.alloc(sizeof(double) * nSrc));
-    AAI_HIP(dDst.alloc(sizeof(double) * nDst));
-    AAI_HIP(upload(dSrc, src, src_stride, g.W, g.H, sizeof(double)));
-    AAI_TRY(enqueue_f64_forward(*req, g, 1, dSrc.as<const double>(), g.W, 0, dDst.as<double>(), g.dW, 0, stream));
-    AAI_HIP(hipStreamSynchronize(stream));
-    AAI_HIP(download(dst, dst_stride, dDst, g.dW, g.dH, sizeof(double)));
-    return finish(*req, g, layout);
+    const HostImage in = src_image(g, 1, src, src_stride, sizeof(double)), out = dst_image(g, 1, dst, dst_stride, sizeof(double));
+    if (!out.bytes()) return finish(*req, g, layout);
+    return round_trip(*req, g, in, out, true, layout, [&](const void *dSrc, void *dDst, hipStream_t stream) {
+        return enqueue_f64_forward(*req, g, 1, static_cast<const double *>(dSrc), in.row, 0, static_cast<double *>(dDst), out.row, 0, stream);
+    });
 }
 
 int aai_adjoint_batch_device_f64(const aai_request *req, int32_t batch, const double *d_gdst, int64_t dst_stride, int64_t dst_image_stride,
                                  double *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(ADJOINT_GENERAL, req, batch, false, 1, d_gdst, dst_stride, d_gsrc, src_stride, g));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue_f64_adjoint(*req, g, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    AAI_TRY(check_adjoint(ADJOINT_GENERAL, req, batch, false, 1, nullptr, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    return device_tail(batch == 0, [&] {
+        return enqueue_f64_adjoint(*req, g, batch, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream);
+    });
 }
 
 int aai_adjoint_f64(const aai_request *req, const double *gdst, int64_t dst_stride, double *gsrc, int64_t src_stride, aai_layout *layout)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(ADJOINT_GENERAL, req, 1, false, 1, gdst, dst_stride, gsrc, src_stride, g));
+    AAI_TRY(check_adjoint(ADJOINT_GENERAL, req, 1, false, 1, nullptr, gdst, dst_stride, gsrc, src_stride, g));
     AAI_TRY(require_device());
-    DeviceBuffer dGdst, dGsrc;
-    hipStream_t stream = nullptr;
-    AAI_HIP(dGdst.alloc(sizeof(double) * (size_t)g.dW * g.dH));
-    AAI_HIP(dGsrc.alloc(sizeof(double) * (size_t)g.W * g.H));
-    AAI_HIP(upload(dGdst, gdst, dst_stride, g.dW, g.dH, sizeof(double)));
-    AAI_TRY(enqueue_f64_adjoint(*req, g, 1, dGdst.as<const double>(), g.dW, 0, dGsrc.as<double>(), g.W, 0, stream));
-    AAI_HIP(hipStreamSynchronize(stream));
-    AAI_HIP(download(gsrc, src_stride, dGsrc, g.W, g.H, sizeof(double)));
-    return finish(*req, g, layout);
+    const HostImage in = dst_image(g, 1, gdst, dst_stride, sizeof(double)), out = src_image(g, 1, gsrc, src_stride, sizeof(double));
+    return round_trip(*req, g, in, out, true, layout, [&](const void *dGdst, void *dGsrc, hipStream_t stream) {
+        return enqueue_f64_adjoint(*req, g, 1, static_cast<const double *>(dGdst), in.row, 0, static_cast<double *>(dGsrc), out.row, 0, stream);
+    });
 }
 
 // The checks of aai_resample_batch_device_f32 in its order -- that entry reports its strides from enqueue(), behind the device check, and so
@@ -590,12 +612,9 @@ int aai_resample_half_batch_device(const aai_request *req, int32_t batch, int32_
     AAI_TRY(check_batch(batch));
     AAI_TRY(request_geometry(*req, g));
     AAI_TRY(check_pointers(d_src, d_dst));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(check_strides(g, 1, src_stride, dst_stride));
-    AAI_TRY(enqueue_half(*req, g, batch, 1, half_dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    return device_tail(batch == 0, [&] { return check_strides(g, 1, src_stride, dst_stride); }, [&] {
+        return enqueue_half(*req, g, batch, 1, half_dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream);
+    });
 }
 
 // (a host entry: the checks of aai_resample_host)
@@ -608,17 +627,9 @@ int aai_resample_half_host(const aai_request *req, int32_t half_dtype, const voi
     AAI_TRY(check_pointers(src, dst));
     AAI_TRY(check_strides(g, 1, src_stride, dst_stride));
     AAI_TRY(require_device());
-    const size_t nSrc = (size_t)g.W * g.H, nDst = (size_t)g.dW * g.dH;
-    if (!nDst) return finish(*req, g, layout);
-    DeviceBuffer dSrc, dDst;
-    hipStream_t stream = nullptr;
-    AAI_HIP(dSrc.alloc(sizeof(uint16_t) * nSrc));
-    AAI_HIP(dDst.alloc(sizeof(uint16_t) * nDst));
-    AAI_HIP(upload(dSrc, src, src_stride, g.W, g.H, sizeof(uint16_t)));
-    AAI_TRY(enqueue_half(*req, g, 1, 1, half_dtype, dSrc.p, g.W, 0, dDst.p, g.dW, 0, stream));
-    AAI_HIP(hipStreamSynchronize(stream));
-    AAI_HIP(download(dst, dst_stride, dDst, g.dW, g.dH, sizeof(uint16_t)));
-    return finish(*req, g, layout);
+    return narrow_round_trip(*req, g, 1, sizeof(uint16_t), src, src_stride, dst, dst_stride, layout, [&](const void *dSrc, void *dDst, hipStream_t stream) {
+        return enqueue_half(*req, g, 1, 1, half_dtype, dSrc, g.W, 0, dDst, g.dW, 0, stream);
+    });
 }
 
 // ---- include/aai_half_interleaved.h: the checks of aai_resample_interleaved_device / _host in their order, like the integer entries
@@ -634,12 +645,9 @@ int aai_resample_half_interleaved_device(const aai_request *req, int32_t batch, 
     AAI_TRY(request_geometry(*req, g));
     AAI_TRY(check_row_length(g, channels));
     if (batch > 0 && g.dW > 0 && g.dH > 0) AAI_TRY(check_pointers(d_src, d_dst));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(check_strides(g, channels, src_stride, dst_stride));
-    AAI_TRY(enqueue_half(*req, g, batch, channels, half_dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    return device_tail(batch == 0, [&] { return check_strides(g, channels, src_stride, dst_stride); }, [&] {
+        return enqueue_half(*req, g, batch, channels, half_dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream);
+    });
 }
 
 int aai_resample_half_interleaved_host(const aai_request *req, int32_t channels, int32_t half_dtype, const void *src, int64_t src_stride, void *dst,
@@ -654,17 +662,9 @@ int aai_resample_half_interleaved_host(const aai_request *req, int32_t channels,
     AAI_TRY(check_row_length(g, channels));
     AAI_TRY(check_strides(g, channels, src_stride, dst_stride));
     AAI_TRY(require_device());
-    const int64_t rowSrc = (int64_t)g.W * channels, rowDst = (int64_t)g.dW * channels;
-    if (!rowDst || !g.dH) return finish(*req, g, layout);
-    DeviceBuffer dSrc, dDst;
-    hipStream_t stream = nullptr;
-    AAI_HIP(dSrc.alloc(sizeof(uint16_t) * (size_t)rowSrc * g.H));
-    AAI_HIP(dDst.alloc(sizeof(uint16_t) * (size_t)rowDst * g.dH));
-    AAI_HIP(upload(dSrc, src, src_stride, rowSrc, g.H, sizeof(uint16_t)));
-    AAI_TRY(enqueue_half(*req, g, 1, channels, half_dtype, dSrc.p, rowSrc, 0, dDst.p, rowDst, 0, stream));
-    AAI_HIP(hipStreamSynchronize(stream));
-    AAI_HIP(download(dst, dst_stride, dDst, rowDst, g.dH, sizeof(uint16_t)));
-    return finish(*req, g, layout);
+    return narrow_round_trip(*req, g, channels, sizeof(uint16_t), src, src_stride, dst, dst_stride, layout, [&](const void *dSrc, void *dDst, hipStream_t stream) {
+        return enqueue_half(*req, g, 1, channels, half_dtype, dSrc, (int64_t)g.W * channels, 0, dDst, (int64_t)g.dW * channels, 0, stream);
+    });
 }
 
 // The checks of aai_resample_interleaved_device in its order -- that entry reports its strides from enqueue(), behind the device check, and
@@ -680,12 +680,9 @@ int aai_resample_int_batch_device(const aai_request *req, int32_t batch, int32_t
     AAI_TRY(request_geometry(*req, g));
     AAI_TRY(check_row_length(g, channels));
     if (batch > 0 && g.dW > 0 && g.dH > 0) AAI_TRY(check_pointers(d_src, d_dst));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(check_strides(g, channels, src_stride, dst_stride));
-    AAI_TRY(enqueue_int(*req, g, batch, channels, dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    return device_tail(batch == 0, [&] { return check_strides(g, channels, src_stride, dst_stride); }, [&] {
+        return enqueue_int(*req, g, batch, channels, dtype, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream);
+    });
 }
 
 // (a host entry: the checks of aai_resample_interleaved_host)
@@ -701,18 +698,9 @@ int aai_resample_int_host(const aai_request *req, int32_t channels, int32_t dtyp
     AAI_TRY(check_row_length(g, channels));
     AAI_TRY(check_strides(g, channels, src_stride, dst_stride));
     AAI_TRY(require_device());
-    const size_t elem = aai::src_elem_size(dtype);
-    const int64_t rowSrc = (int64_t)g.W * channels, rowDst = (int64_t)g.dW * channels;
-    if (!rowDst || !g.dH) return finish(*req, g, layout);
-    DeviceBuffer dSrc, dDst;
-    hipStream_t stream = nullptr;
-    AAI_HIP(dSrc.alloc(elem * (size_t)rowSrc * g.H));
-    AAI_HIP(dDst.alloc(elem * (size_t)rowDst * g.dH));
-    AAI_HIP(upload(dSrc, src, src_stride, rowSrc, g.H, elem));
-    AAI_TRY(enqueue_int(*req, g, 1, channels, dtype, dSrc.p, rowSrc, 0, dDst.p, rowDst, 0, stream));
-    AAI_HIP(hipStreamSynchronize(stream));
-    AAI_HIP(download(dst, dst_stride, dDst, rowDst, g.dH, elem));
-    return finish(*req, g, layout);
+    return narrow_round_trip(*req, g, channels, aai::src_elem_size(dtype), src, src_stride, dst, dst_stride, layout, [&](const void *dSrc, void *dDst, hipStream_t stream) {
+        return enqueue_int(*req, g, 1, channels, dtype, dSrc, (int64_t)g.W * channels, 0, dDst, (int64_t)g.dW * channels, 0, stream);
+    });
 }
 
 int aai_adjoint_prepare(const aai_request *req) { return adjoint_prepare(ADJOINT_PLANNED, req); }
@@ -788,31 +776,22 @@ int aai_adjoint_half_device(const aai_request *req, int32_t batch, int32_t chann
                             int64_t dst_image_stride, void *d_gsrc, int64_t src_stride, int64_t src_image_stride, void *stream)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(ADJOINT_SEPARABLE, req, batch, true, channels, d_gdst, dst_stride, d_gsrc, src_stride, g, &half_dtype));
-    if (batch == 0) { g_lastError.clear(); return AAI_OK; }
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue_adjoint_half(*req, g, batch, channels, half_dtype, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride,
-                                 (hipStream_t)stream));
-    g_lastError.clear();
-    return AAI_OK;
+    AAI_TRY(check_adjoint(ADJOINT_SEPARABLE, req, batch, true, channels, &half_dtype, d_gdst, dst_stride, d_gsrc, src_stride, g));
+    return device_tail(batch == 0, [&] {
+        return enqueue_adjoint_half(*req, g, batch, channels, half_dtype, d_gdst, dst_stride, dst_image_stride, d_gsrc, src_stride, src_image_stride, (hipStream_t)stream);
+    });
 }
 
 int aai_adjoint_half_host(const aai_request *req, int32_t channels, int32_t half_dtype, const void *gdst, int64_t dst_stride, void *gsrc, int64_t src_stride,
                           aai_layout *layout)
 {
     aai::Geometry g;
-    AAI_TRY(check_adjoint(ADJOINT_SEPARABLE, req, 1, true, channels, gdst, dst_stride, gsrc, src_stride, g, &half_dtype));
+    AAI_TRY(check_adjoint(ADJOINT_SEPARABLE, req, 1, true, channels, &half_dtype, gdst, dst_stride, gsrc, src_stride, g));
     AAI_TRY(require_device());
-    const int64_t rowDst = (int64_t)g.dW * channels, rowSrc = (int64_t)g.W * channels;
-    DeviceBuffer dGdst, dGsrc;
-    hipStream_t stream = nullptr;
-    AAI_HIP(dGdst.alloc(sizeof(uint16_t) * (size_t)rowDst * g.dH));
-    AAI_HIP(dGsrc.alloc(sizeof(uint16_t) * (size_t)rowSrc * g.H));
-    AAI_HIP(upload(dGdst, gdst, dst_stride, rowDst, g.dH, sizeof(uint16_t)));
-    AAI_TRY(enqueue_adjoint_half(*req, g, 1, channels, half_dtype, dGdst.p, rowDst, 0, dGsrc.p, rowSrc, 0, stream));
-    AAI_HIP(hipStreamSynchronize(stream));
-    AAI_HIP(download(gsrc, src_stride, dGsrc, rowSrc, g.H, sizeof(uint16_t)));
-    return finish(*req, g, layout);
+    const HostImage in = dst_image(g, channels, gdst, dst_stride, sizeof(uint16_t)), out = src_image(g, channels, gsrc, src_stride, sizeof(uint16_t));
+    return round_trip(*req, g, in, out, true, layout, [&](const void *dGdst, void *dGsrc, hipStream_t stream) {
+        return enqueue_adjoint_half(*req, g, 1, channels, half_dtype, dGdst, in.row, 0, dGsrc, out.row, 0, stream);
+    });
 }
 
 int aai_adjoint_sample_batch_device_f32(const aai_request *req, int32_t batch,
@@ -882,10 +861,9 @@ int aai_resample_interleaved_device(const aai_request *req, int32_t batch, int32
     AAI_TRY(request_geometry(*req, g));
     AAI_TRY(check_row_length(g, channels));
     if (batch > 0 && g.dW > 0 && g.dH > 0) AAI_TRY(check_pointers(d_src, d_dst));
-    AAI_TRY(require_device());
-    AAI_TRY(enqueue(*req, g, batch, d_src, src_dtype, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream, -1, -1, channels));
-    g_lastError.clear();
-    return AAI_OK;
+    return device_tail(false, [&] {
+        return enqueue(*req, g, batch, d_src, src_dtype, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, (hipStream_t)stream, -1, -1, channels);
+    });
 }
 
 int aai_resample_interleaved_host(const aai_request *req, int32_t channels, const void *src, int32_t src_dtype, int64_t src_stride,

@@ -931,6 +931,58 @@ int enqueue_f64_adjoint(const aai_request &rq, const Geometry &g, int batch, con
     return for_each_adjoint_chunk(batch, dGdst, dstImageStride, dGsrc, srcImageStride, imageBytes, device, stream, name, false, launch);
 }
 
+// ---- forwarding a narrow-element call through dense fp32 scratch: the second route of enqueue_narrow and enqueue_adjoint_half
+// One side of it: the caller's images of raw `type` elements (view: strides in elements) and the shape of their dense fp32 twins.
+struct NarrowSide {
+    const void *p;
+    aai::ImageView view;
+    int64_t row;      // elements per dense row
+    int rows;
+    size_t count() const { return (size_t)row * (size_t)rows; }
+    const char *image(int type, int b) const { return static_cast<const char *>(p) + (int64_t)b * view.imageStride * (int64_t)aai::narrow_elem_size(type); }
+};
+// Per chunk of chunk_images(): (widen: `in` widened into scratch,) inner(nb, in32, out32) -> int, the fp32 entry's launches on dense
+// images (image b of the chunk at b * in.count() / b * out.count(); !widen: in32 is the caller's own image, which that entry reads),
+// and one conversion of out32 into `out`.  The scratch is stream-ordered from `device`'s pool: all of a chunk's widened inputs, each
+// rounded up to 256 bytes, then all its outputs.  aai_last_kernel(): what inner() left there, `suffix` appended.  A failed inner()
+// keeps its error text, whatever the free says; a failed launch is reported under its kernel's name.
+template <typename Inner>
+static int through_fp32_scratch(int type, bool widen, const NarrowSide &in, const NarrowSide &out, int batch, int device, const char *suffix,
+                                hipStream_t stream, Inner inner)
+{
+    const size_t inBytes = widen ? (in.count() * sizeof(float) + 255) & ~(size_t)255 : 0, outBytes = (out.count() * sizeof(float) + 255) & ~(size_t)255;
+    const int chunk = chunk_images(batch, inBytes + outBytes);
+    hipMemPool_t pool = nullptr;
+    const int rp = adjoint_scratch_pool(device, &pool);
+    if (rp != AAI_OK) return rp;
+    char *scratch = nullptr;
+    AAI_HIP(hipMallocFromPoolAsync((void **)&scratch, (inBytes + outBytes) * (size_t)chunk, pool, stream));
+    float *in32 = reinterpret_cast<float *>(scratch), *out32 = reinterpret_cast<float *>(scratch + inBytes * (size_t)chunk);
+    const char *const storeName = aai::narrow_is_half(type) ? "aai_half_narrow_kernel" : "aai_int_quantize_kernel";
+    const char *what = storeName;
+    hipError_t e = hipSuccess;
+    int rl = AAI_OK;
+    for (int b0 = 0; b0 < batch && e == hipSuccess && rl == AAI_OK; b0 += chunk) {
+        const int nb = std::min(batch - b0, chunk);
+        if (widen) {
+            what = "aai_half_widen_kernel";
+            if (in.count()) e = aai::launch_narrow_widen(type, in.image(type, b0), in.view, in32, (int)in.row, in.rows, nb, stream);
+            if (e != hipSuccess) break;
+        }
+        rl = inner(nb, widen ? (const void *)in32 : (const void *)in.image(type, b0), out32);
+        if (rl != AAI_OK) break;
+        what = storeName;
+        e = aai::launch_narrow_store(type, out32, const_cast<char *>(out.image(type, b0)), out.view, (int)out.row, out.rows, nb, stream);
+    }
+    const std::string lastError = g_lastError;      // (of a failed inner(): hipFreeAsync below must not replace it)
+    const hipError_t ef = hipFreeAsync(scratch, stream);
+    if (rl != AAI_OK) return fail(rl, lastError);
+    g_lastKernel += suffix;
+    if (e != hipSuccess) return hip_fail(e, what);
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    return AAI_OK;
+}
+
 // ---- the narrow-element paths (include/aai_half.h, include/aai_half_interleaved.h, include/aai_int.h; aai_axis_narrow.hip)
 // `type`: aai::NarrowType.  `srcType` is what enqueue() reads on the forwarding route and what keys the plan: the caller's u8 / u16
 // image itself, or the dense fp32 scratch a half image is widened into.
@@ -967,38 +1019,10 @@ static int enqueue_narrow(const aai_request &rq, const Geometry &g, int batch, i
     }
     // forwarding: (half: widen,) the fp32 entry's launches into dense fp32 scratch, one conversion -- the bits of
     // narrow(fp32 entry(widen(src))) and of quantize(fp32 entry(src))
-    const size_t srcBytes = half ? (nSrc * sizeof(float) + 255) & ~(size_t)255 : 0, dstBytes = (nDst * sizeof(float) + 255) & ~(size_t)255;
-    const int chunk = chunk_images(batch, srcBytes + dstBytes);
-    hipMemPool_t pool = nullptr;
-    const int rp = adjoint_scratch_pool(p->device, &pool);
-    if (rp != AAI_OK) return rp;
-    char *scratch = nullptr;
-    AAI_HIP(hipMallocFromPoolAsync((void **)&scratch, (srcBytes + dstBytes) * (size_t)chunk, pool, stream));
-    // (dense fp32 images, image b of a chunk at b * nSrc / b * nDst: all the widened sources of a chunk, then all its outputs)
-    float *s32 = reinterpret_cast<float *>(scratch), *d32 = reinterpret_cast<float *>(scratch + srcBytes * (size_t)chunk);
-    const char *const storeName = half ? "aai_half_narrow_kernel" : "aai_int_quantize_kernel";
-    const char *what = storeName;
-    int rl = AAI_OK;
-    for (int b0 = 0; b0 < batch && e == hipSuccess && rl == AAI_OK; b0 += chunk) {
-        const int nb = std::min(batch - b0, chunk);
-        const char *in = src + (int64_t)b0 * srcImageStride * elem;
-        if (half) {
-            what = "aai_half_widen_kernel";
-            e = aai::launch_narrow_widen(type, in, sv, s32, (int)rowSrc, g.H, nb, stream);
-            if (e != hipSuccess) break;
-        }
-        rl = enqueue(rq, g, nb, half ? (const void *)s32 : in, srcType, inStride, inImageStride, d32, rowDst, (int64_t)nDst, stream, -1, -1, channels);
-        if (rl != AAI_OK) break;
-        what = storeName;
-        e = aai::launch_narrow_store(type, d32, dst + (int64_t)b0 * dstImageStride * elem, dv, (int)rowDst, g.dH, nb, stream);
-    }
-    const std::string lastError = g_lastError;      // (of a failed enqueue(): hipFreeAsync below must not replace it)
-    const hipError_t ef = hipFreeAsync(scratch, stream);
-    if (rl != AAI_OK) return fail(rl, lastError);
-    g_lastKernel += half ? "+widened" : "+quantized";
-    if (e != hipSuccess) return hip_fail(e, what);
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    return AAI_OK;
+    const NarrowSide in{dSrc, sv, rowSrc, g.H}, out{dDst, dv, rowDst, g.dH};
+    return through_fp32_scratch(type, half, in, out, batch, p->device, half ? "+widened" : "+quantized", stream, [&](int nb, const void *in32, float *out32) {
+        return enqueue(rq, g, nb, in32, srcType, inStride, inImageStride, out32, rowDst, (int64_t)nDst, stream, -1, -1, channels);
+    });
 }
 
 // ---- the half-precision adjoint (include/aai_adjoint_half.h; aai_axis_adjoint_narrow.hip): routes in aai_engine.hpp
@@ -1040,40 +1064,14 @@ int enqueue_adjoint_half(const aai_request &rq, const Geometry &g, int batch, in
         }
     }
     // FORWARDING: widen gdst into dense fp32 scratch, the code behind aai_adjoint_planned_interleaved_device_f32 into a dense fp32 gsrc,
-    // one rounding into the caller's buffer -- the bits of narrow(fp32 entry(widen(gdst)))
-    const int64_t rowDst = (int64_t)g.dW * channels, rowSrc = (int64_t)g.W * channels;
-    const size_t nDst = (size_t)rowDst * (size_t)g.dH, nSrc = (size_t)rowSrc * (size_t)g.H;
-    const size_t dstBytes = (nDst * sizeof(float) + 255) & ~(size_t)255, srcBytes = (nSrc * sizeof(float) + 255) & ~(size_t)255;
-    const int chunk = chunk_images(batch, dstBytes + srcBytes);
+    // one rounding into the caller's buffer -- the bits of narrow(fp32 entry(widen(gdst))).  (An empty gdst is not widened: nothing to launch.)
+    const NarrowSide in{dGdst, dv, (int64_t)g.dW * channels, g.dH}, out{dGsrc, sv, (int64_t)g.W * channels, g.H};
     int device = 0;
     AAI_HIP(hipGetDevice(&device));
-    hipMemPool_t pool = nullptr;
-    const int rp = adjoint_scratch_pool(device, &pool);
-    if (rp != AAI_OK) return rp;
-    char *scratch = nullptr;
-    AAI_HIP(hipMallocFromPoolAsync((void **)&scratch, (dstBytes + srcBytes) * (size_t)chunk, pool, stream));
-    // (dense fp32 images, image b of a chunk at b * nDst / b * nSrc: all the widened gradients of a chunk, then all its results)
-    float *d32 = reinterpret_cast<float *>(scratch), *s32 = reinterpret_cast<float *>(scratch + dstBytes * (size_t)chunk);
-    const char *what = "aai_half_widen_kernel";
-    hipError_t e = hipSuccess;
-    int rl = AAI_OK;
-    for (int b0 = 0; b0 < batch && e == hipSuccess && rl == AAI_OK; b0 += chunk) {
-        const int nb = std::min(batch - b0, chunk);
-        what = "aai_half_widen_kernel";
-        if (nDst) e = aai::launch_narrow_widen(type, gd + (int64_t)b0 * dstImageStride * elem, dv, d32, (int)rowDst, g.dH, nb, stream);
-        if (e != hipSuccess) break;
-        rl = enqueue_adjoint(ADJOINT_SEPARABLE, rq, g, nb, channels, d32, rowDst, (int64_t)nDst, s32, rowSrc, (int64_t)nSrc, stream);
-        if (rl != AAI_OK) break;
-        what = "aai_half_narrow_kernel";
-        e = aai::launch_narrow_store(type, s32, gs + (int64_t)b0 * srcImageStride * elem, sv, (int)rowSrc, g.H, nb, stream);
-    }
-    const std::string lastError = g_lastError;      // (of a failed enqueue_adjoint(): hipFreeAsync below must not replace it)
-    const hipError_t ef = hipFreeAsync(scratch, stream);
-    if (rl != AAI_OK) return fail(rl, lastError);
-    g_lastKernel += "+widened";
-    if (e != hipSuccess) return hip_fail(e, what);
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    return AAI_OK;
+    return through_fp32_scratch(type, true, in, out, batch, device, "+widened", stream, [&](int nb, const void *gd32, float *gs32) {
+        return enqueue_adjoint(ADJOINT_SEPARABLE, rq, g, nb, channels, static_cast<const float *>(gd32), in.row, (int64_t)in.count(), gs32, out.row,
+                               (int64_t)out.count(), stream);
+    });
 }
 
 int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int channels, int halfType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,

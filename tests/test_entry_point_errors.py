@@ -1,11 +1,12 @@
-"""CPU: which (return code, aai_last_error()) every compute entry point of include/aai.h reports for a faulty call.
+"""CPU: which (return code, aai_last_error()) every compute entry point of include/*.h reports for a faulty call.
 
 Every argument error is reported before the device is touched, so none of this needs a GPU.  Each entry point is called
 with a valid call, with every single fault it can be given, and with every pair of faults (which pins the ORDER of its
 checks: a request with two faults reports the one checked first).  The expected values are a recording, not a
-specification: tests/golden/entry_point_errors.json holds what the library answered when the table was made
-(`python tests/test_entry_point_errors.py --record` rewrites it from the library in the tree), and a change of the
-host code that is meant to keep behaviour must reproduce it.  Device pointers are fake non-null integers: nothing
+specification: tests/golden/entry_point_errors.json (the entries of include/aai.h) and entry_point_errors_typed.json (those
+of the eleven extension headers) hold what the library answered when the tables were made
+(`python tests/test_entry_point_errors.py --record` rewrites them from the library in the tree), and a change of the
+host code that is meant to keep behaviour must reproduce them.  Device pointers are fake non-null integers: nothing
 dereferences them before the device check, and a probe whose recorded answer is "no device" is not run where there is one.
 """
 import ctypes
@@ -18,6 +19,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 TABLE = os.path.join(HERE, "golden", "entry_point_errors.json")
+TYPED_TABLE = os.path.join(HERE, "golden", "entry_point_errors_typed.json")
 
 FAKE_SRC, FAKE_DST = 0x10000, 0x20000
 BIG = 4096          # a row stride no smaller than any row of the base request, in elements (4 channels included)
@@ -122,17 +124,122 @@ FAULTS = {
     "negative_row0": {"row0": -1},
 }
 
+# The entries of the extension headers, recorded in TYPED_TABLE.  They take the faults above and a few of their own (TYPED_FAULTS),
+# which the entries of include/aai.h are not probed with: their table was recorded without them.
+_BATCH = [("src", FAKE_SRC), ("src_stride", BIG), ("src_image_stride", BIG * BIG), ("dst", FAKE_DST), ("dst_stride", BIG), ("dst_image_stride", BIG * BIG),
+          ("stream", None)]
+_ADJ_BATCH = [("dst", FAKE_DST), ("dst_stride", BIG), ("dst_image_stride", BIG * BIG), ("src", FAKE_SRC), ("src_stride", BIG), ("src_image_stride", BIG * BIG),
+              ("stream", None)]
+_ADJ_HOST = [("dst", FAKE_DST), ("dst_stride", BIG), ("src", FAKE_SRC), ("src_stride", BIG), ("layout", None)]
+_RQ, _RQ_B, _RQ_BC, _RQ_C = [("req", 1)], [("req", 1), ("batch", 2)], [("req", 1), ("batch", 2), ("channels", 3)], [("req", 1), ("channels", 3)]
+TYPED_ENTRIES = {
+    # include/aai_f64.h
+    "aai_resample_batch_device_f64": _RQ_B + _BATCH,
+    "aai_resample_exact_f64": _RQ + _HOST,
+    "aai_adjoint_batch_device_f64": _RQ_B + _ADJ_BATCH,
+    "aai_adjoint_f64": _RQ + _ADJ_HOST,
+    # include/aai_half.h, aai_half_interleaved.h, aai_int.h
+    "aai_resample_half_batch_device": _RQ_B + [("half_dtype", 1)] + _BATCH,
+    "aai_resample_half_host": _RQ + [("half_dtype", 2)] + _HOST,
+    "aai_resample_half_interleaved_device": _RQ_BC + [("half_dtype", 1)] + _BATCH,
+    "aai_resample_half_interleaved_host": _RQ_C + [("half_dtype", 2)] + _HOST,
+    "aai_resample_int_batch_device": _RQ_BC + [("dtype", 1)] + _BATCH,
+    "aai_resample_int_host": _RQ_C + [("dtype", 2)] + _HOST,
+    # include/aai_adjoint_half.h
+    "aai_adjoint_half_device": _RQ_BC + [("half_dtype", 1)] + _ADJ_BATCH,
+    "aai_adjoint_half_host": _RQ_C + [("half_dtype", 2)] + _ADJ_HOST,
+    # include/aai_adjoint_planned.h, aai_adjoint_rotated.h
+    "aai_adjoint_prepare": _RQ,
+    "aai_adjoint_planned_batch_device_f32": _RQ_B + _ADJ_BATCH,
+    "aai_adjoint_planned_f32": _RQ + _ADJ_HOST,
+    "aai_adjoint_rotated_prepare": _RQ,
+    "aai_adjoint_rotated_batch_device_f32": _RQ_B + _ADJ_BATCH,
+    "aai_adjoint_rotated_f32": _RQ + _ADJ_HOST,
+    # include/aai_adjoint_interleaved.h, aai_adjoint_rotated_interleaved.h, aai_adjoint_planned_interleaved.h
+    "aai_adjoint_interleaved_device_f32": _RQ_BC + _ADJ_BATCH,
+    "aai_adjoint_interleaved_f32": _RQ_C + _ADJ_HOST,
+    "aai_adjoint_rotated_interleaved_device_f32": _RQ_BC + _ADJ_BATCH,
+    "aai_adjoint_rotated_interleaved_f32": _RQ_C + _ADJ_HOST,
+    "aai_adjoint_planned_interleaved_device_f32": _RQ_BC + _ADJ_BATCH,
+    "aai_adjoint_planned_interleaved_f32": _RQ_C + _ADJ_HOST,
+    # include/aai_adjoint_sample.h
+    "aai_adjoint_sample_batch_device_f32": _RQ_B + _ADJ_BATCH,
+    "aai_adjoint_sample_f32": _RQ + _ADJ_HOST,
+    "aai_adjoint_sample_interleaved_device_f32": _RQ_BC + _ADJ_BATCH,
+    "aai_adjoint_sample_interleaved_f32": _RQ_C + _ADJ_HOST,
+}
+# (the samplers' adjoint takes the bilinear and bicubic modes only: its valid call is the base request in bilinear mode)
+REQUEST = {e: {"mode": 3} for e in TYPED_ENTRIES if e.startswith("aai_adjoint_sample_")}
+TYPED_FAULTS = dict(FAULTS, **{
+    "bad_half_dtype": {"half_dtype": 7},
+    "bad_int_dtype": {"dtype": 7},
+    "f32_int_dtype": {"dtype": 0},                                            # (an element type of the fp32 entries, none of the integer ones)
+    "mode_area": {"rq.mode": 1},                                              # (faults for the samplers' adjoint only; valid elsewhere)
+    "mode_fast": {"rq.mode": 2},
+    "mode_bicubic": {"rq.mode": 4},                                           # (a fault for the area adjoint and the f64 forward)
+})
+
+
+def _args(entry):
+    return ENTRIES[entry] if entry in ENTRIES else TYPED_ENTRIES[entry]
+
+
+def _faults(entry):
+    return FAULTS if entry in ENTRIES else TYPED_FAULTS
+
+
+# TYPED_TABLE holds its 6,046 probes packed, one entry point per line, and names everything it packs:
+#   "faults"   the fault names that the numbers below stand for
+#   "answers"  the distinct [return code, text] pairs that the numbers below stand for
+#   entry  ->  "singles": the faults that apply to it, "valid": the answer without a fault, "single": the answer per single fault, and
+#              "pairs": row i holds the answers of the pairs (singles[i], singles[i + 1 + j]), null where the two are not paired
+def pack(tables):
+    """{entry: {probe: [rc, text]}} -> the packed form"""
+    names, answers = list(TYPED_FAULTS), []
+
+    def number(answer):
+        if answer not in answers:
+            answers.append(answer)
+        return answers.index(answer)
+
+    entries = {}
+    for entry, t in tables.items():
+        s = [f for f in names if f in t]
+        entries[entry] = {"singles": [names.index(f) for f in s], "valid": number(t["valid"]), "single": [number(t[f]) for f in s],
+                          "pairs": [[number(t[a + "+" + b]) if a + "+" + b in t else None for b in s[i + 1:]] for i, a in enumerate(s)]}
+    return {"faults": names, "answers": answers, "entries": entries}
+
+
+def unpack(packed):
+    """the packed form -> {entry: {probe: [rc, text]}}"""
+    names, answers, tables = packed["faults"], packed["answers"], {}
+    for entry, e in packed["entries"].items():
+        s = [names[i] for i in e["singles"]]
+        t = {"valid": answers[e["valid"]]}
+        t.update({f: answers[k] for f, k in zip(s, e["single"])})
+        for i, row in enumerate(e["pairs"]):
+            t.update({s[i] + "+" + s[i + 1 + j]: answers[k] for j, k in enumerate(row) if k is not None})
+        tables[entry] = t
+    return tables
+
+
+def load_table(entry):
+    """{entry: {probe: [rc, text]}} of the golden file that holds `entry`"""
+    return json.load(open(TABLE)) if entry in ENTRIES else unpack(json.load(open(TYPED_TABLE)))
+
+
 def _applies(fault, entry):
-    names = [n for n, _ in ENTRIES[entry]]
-    return all((k.startswith("rq.") and "req" in names) or k in names for k in FAULTS[fault])
+    names = [n for n, _ in _args(entry)]
+    return all((k.startswith("rq.") and "req" in names) or k in names for k in _faults(entry)[fault])
 
 
 def probes(entry):
     """the fault combinations of an entry point: (), every single fault, every pair that replaces different things"""
-    singles = [f for f in FAULTS if _applies(f, entry)]
+    faults = _faults(entry)
+    singles = [f for f in faults if _applies(f, entry)]
     out = [()] + [(f,) for f in singles]
     for a, b in itertools.combinations(singles, 2):
-        ka, kb = set(FAULTS[a]), set(FAULTS[b])
+        ka, kb = set(faults[a]), set(faults[b])
         if ka & kb:
             continue
         if ("req" in ka and any(k.startswith("rq.") for k in kb)) or ("req" in kb and any(k.startswith("rq.") for k in ka)):
@@ -143,9 +250,9 @@ def probes(entry):
 
 def call(lib, L, entry, faults):
     """-> [return code, aai_last_error()] of one probe"""
-    fields, args = dict(BASE), dict(ENTRIES[entry])
+    fields, args = dict(BASE, **REQUEST.get(entry, {})), dict(_args(entry))
     for f in faults:
-        for k, v in FAULTS[f].items():
+        for k, v in _faults(entry)[f].items():
             if k.startswith("rq."):
                 fields[k[3:]] = v
             else:
@@ -156,34 +263,39 @@ def call(lib, L, entry, faults):
     # start from an empty error text: a successful query clears it
     lay = L.Layout()
     assert lib.aai_query(ctypes.byref(L.Request(**BASE)), ctypes.byref(lay)) == L.OK and lib.aai_last_error() == b""
-    rc = getattr(lib, entry)(*[args[n] for n, _ in ENTRIES[entry]])
+    rc = getattr(lib, entry)(*[args[n] for n, _ in _args(entry)])
     return [rc, lib.aai_last_error().decode()]
 
 
-def record(lib, L):
-    return {entry: {"+".join(p) or "valid": call(lib, L, entry, p) for p in probes(entry)} for entry in ENTRIES}
+def record(lib, L, entries):
+    return {entry: {"+".join(p) or "valid": call(lib, L, entry, p) for p in probes(entry)} for entry in entries}
 
 
 def test_every_compute_entry_point_is_probed():
     import re
-    text = open(os.path.join(os.path.dirname(HERE), "include", "aai.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(aai_[a-z0-9_]+)\s*\(", text))
+    import glob
+    headers = sorted(glob.glob(os.path.join(os.path.dirname(HERE), "include", "*.h")))
+    assert len(headers) == 12, headers
+    declared = set()
+    for header in headers:
+        text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
+        declared |= set(re.findall(r"\b(aai_[a-z0-9_]+)\s*\(", text))
     # what is left out computes nothing: queries, device management, the error texts, page-locked allocation
     left_out = {"aai_query", "aai_last_error", "aai_last_kernel", "aai_error_string", "aai_version", "aai_device_count", "aai_set_device",
                 "aai_device_synchronize", "aai_host_alloc", "aai_host_free", "aai_shutdown"}
-    assert declared - left_out == set(ENTRIES)
-    table = json.load(open(TABLE))
-    for entry in ENTRIES:
+    assert not set(ENTRIES) & set(TYPED_ENTRIES)
+    assert declared - left_out == set(ENTRIES) | set(TYPED_ENTRIES)
+    for entry in list(ENTRIES) + list(TYPED_ENTRIES):
+        table = load_table(entry)
         assert sorted(table[entry]) == sorted("+".join(p) or "valid" for p in probes(entry)), entry
         assert len(table[entry]) > 10 and any("+" in k for k in table[entry]), entry
 
 
-@pytest.mark.parametrize("entry", sorted(ENTRIES))
+@pytest.mark.parametrize("entry", sorted(ENTRIES) + sorted(TYPED_ENTRIES))
 def test_entry_point_reports_the_recorded_error(aai, entry):
     from area_average_interpolation_amd import _lib as L
     lib = L.load()
-    table = json.load(open(TABLE))[entry]
+    table = load_table(entry)[entry]
     have_gpu = aai.device_count() > 0
     wrong = []
     for p in probes(entry):
@@ -210,6 +322,10 @@ if __name__ == "__main__":
     if _aai.device_count() > 0:
         sys.exit("record the table on a machine without a GPU: every probe must stop at the device check at the latest")
     with open(TABLE, "w") as f:
-        json.dump(record(_L.load(), _L), f, indent=0, sort_keys=True)
+        json.dump(record(_L.load(), _L, ENTRIES), f, indent=0, sort_keys=True)
         f.write("\n")
-    print("wrote", TABLE)
+    packed = pack(record(_L.load(), _L, sorted(TYPED_ENTRIES)))
+    with open(TYPED_TABLE, "w") as f:      # (one line per entry point)
+        f.write('{"faults": %s,\n"answers": %s,\n"entries": {\n%s\n}}\n' % (json.dumps(packed["faults"]), json.dumps(packed["answers"]), ",\n".join(
+            "%s: %s" % (json.dumps(e), json.dumps(v, separators=(",", ":"))) for e, v in packed["entries"].items())))
+    print("wrote", TABLE, TYPED_TABLE)

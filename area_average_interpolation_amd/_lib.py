@@ -168,6 +168,21 @@ ADJOINT_HALF_SYMBOLS = {
     "aai_adjoint_half_host": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _P, _I64, _LY]),
 }
 
+# the extension header include/ext/aai_convert.h: u8 / u16 images in, a scaled fp32 / fp16 / bf16 image out, interleaved or planar
+LAYOUT_INTERLEAVED, LAYOUT_PLANAR = 0, 1
+
+
+class Convert(ctypes.Structure):
+    """aai_convert: out_type (DTYPE_F32, HALF_F16 or HALF_BF16), out_layout (LAYOUT_*), scale and offset per channel"""
+    _fields_ = [("out_type", ctypes.c_int32), ("out_layout", ctypes.c_int32), ("scale", ctypes.c_float * 4), ("offset", ctypes.c_float * 4)]
+
+
+_CV = ctypes.POINTER(Convert)
+CONVERT_SYMBOLS = {
+    "aai_resample_convert_device": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _I64, _I64, _CV, _P, _I64, _I64, _I64, _P]),
+    "aai_resample_convert_host": (ctypes.c_int, [_RQ, ctypes.c_int32, ctypes.c_int32, _P, _I64, _CV, _P, _I64, _I64, _LY]),
+}
+
 _lib = None
 
 
@@ -191,7 +206,8 @@ def load():
         for name, (res, args) in (list(SYMBOLS.items()) + list(PLANNED_SYMBOLS.items()) + list(INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(ROTATED_ADJOINT_SYMBOLS.items()) + list(ROTATED_INTERLEAVED_ADJOINT_SYMBOLS.items()) +
                                   list(PLANNED_INTERLEAVED_ADJOINT_SYMBOLS.items()) + list(SAMPLE_ADJOINT_SYMBOLS.items()) + list(F64_SYMBOLS.items()) +
-                                  list(HALF_SYMBOLS.items()) + list(INT_SYMBOLS.items()) + list(HALF_INTERLEAVED_SYMBOLS.items()) + list(ADJOINT_HALF_SYMBOLS.items())):
+                                  list(HALF_SYMBOLS.items()) + list(INT_SYMBOLS.items()) + list(HALF_INTERLEAVED_SYMBOLS.items()) + list(ADJOINT_HALF_SYMBOLS.items()) +
+                                  list(CONVERT_SYMBOLS.items())):
             fn = getattr(lib, name)      # AttributeError if the ABI and the header drifted apart
             fn.restype = res
             fn.argtypes = args

@@ -607,6 +607,76 @@ def resample_int_host(src, src_resolution, dst_resolution, src_isocenter, rotati
     return _host_forward(a, C, a.ndim == 3, (src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy), lib.aai_resample_int_host, C, dtype)
 
 
+def make_convert(channels, out_type=L.DTYPE_F32, planar=False, scale=None, offset=None):
+    """aai_convert (include/ext/aai_convert.h) for `channels` channels: out_type DTYPE_F32, HALF_F16 or HALF_BF16; scale / offset a scalar or
+    one value per channel (default 1 and 0)"""
+    def per_channel(v, default):
+        v = default if v is None else v
+        vals = [float(v)] * channels if np.ndim(v) == 0 else [float(x) for x in v]
+        if len(vals) != channels:
+            raise ValueError("scale and offset take a scalar or one value per channel (%d), got %d" % (channels, len(vals)))
+        return vals + [0.0] * (4 - len(vals))
+    if not 1 <= int(channels) <= 4:
+        raise ValueError("channels must be 1..4")
+    cv = L.Convert()
+    cv.out_type, cv.out_layout = int(out_type), L.LAYOUT_PLANAR if planar else L.LAYOUT_INTERLEAVED
+    cv.scale[:] = per_channel(scale, 1.0)
+    cv.offset[:] = per_channel(offset, 0.0)
+    return cv
+
+
+_CONVERT_NP = {L.DTYPE_F32: np.float32, L.HALF_F16: np.float16, L.HALF_BF16: np.uint16}      # (bf16: raw 16-bit elements)
+
+
+def resample_convert_device(request, channels, src_ptr, src_stride, dst_ptr, dst_stride, src_dtype, convert, stream=0, batch=None, src_image_stride=0,
+                            dst_image_stride=0, dst_plane_stride=0):
+    """aai_resample_convert_device (include/ext/aai_convert.h): device-resident 8-bit (src_dtype = DTYPE_U8) or 16-bit (DTYPE_U16) unsigned
+    images of `channels` = 1..4 interleaved channels in, round(fma(resample(src), scale[c], offset[c])) out in convert.out_type, interleaved
+    or planar (make_convert).  Raw device pointers (ints), strides in elements of the respective type, a hipStream_t handle.  All four
+    modes.  Rotations by 0 / 180 degrees in the area / fast modes run one kernel from the integer image to the converted image
+    (last_kernel(): "aai_axis_convert_kernel<u8|u16,f32|f16|bf16>"), everything else runs resample_interleaved_device's launches into fp32
+    scratch and converts ("<fp32 kernel>+converted")."""
+    _check(L.load().aai_resample_convert_device(_ref(request), 1 if batch is None else int(batch), int(channels), int(src_dtype), src_ptr, src_stride,
+                                                src_image_stride, ctypes.byref(convert) if convert is not None else None, dst_ptr, dst_stride, dst_plane_stride,
+                                                dst_image_stride, stream))
+
+
+def resample_convert_host(src, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE, out_type=L.DTYPE_F32,
+                          planar=False, scale=None, offset=None):
+    """Host-buffer resample-and-convert (aai_resample_convert_host): src is a [H, W] or [H, W, C] (C = 1..4, interleaved) image of np.uint8 or
+    np.uint16; the result is [dH, dW, C] (interleaved; [dH, dW] for a 2-D src) or [C, dH, dW] (planar) of np.float32, np.float16 or -- bf16 --
+    raw np.uint16 elements.  The bits of resample_convert_device.
+
+    Returns (code, message, dst ndarray or None, (dstIsoX, dstIsoY) or None, Layout or None)."""
+    lib = L.load()
+    a = np.asarray(src)
+    if a.dtype not in (np.uint8, np.uint16):
+        raise TypeError("resample_convert_host takes np.uint8 or np.uint16 images, got %s" % a.dtype)
+    if out_type not in _CONVERT_NP:
+        raise ValueError("out_type must be DTYPE_F32, HALF_F16 or HALF_BF16")
+    dtype = L.DTYPE_U8 if a.dtype == np.uint8 else L.DTYPE_U16
+    if a.ndim not in (2, 3):
+        if a.size != 0:
+            raise ValueError("src must be an image [H, W] or [H, W, C]")
+        a = a.reshape(0, 0)        # the reference's two "no data" errors (Source.cpp:123-132)
+    a = np.ascontiguousarray(a)
+    H, W = a.shape[:2]
+    C = a.shape[2] if a.ndim == 3 else 1
+    cv = make_convert(C, out_type, planar, scale, offset)
+    rq = make_request(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    rc, msg, lay = query(rq)
+    if rc != L.OK:
+        return rc, msg, None, None, None
+    dH, dW = lay.dst_height, lay.dst_width
+    dst = np.empty((C, dH, dW) if planar else ((dH, dW, C) if a.ndim == 3 else (dH, dW)), dtype=_CONVERT_NP[out_type])
+    out_lay = L.Layout()
+    rc = lib.aai_resample_convert_host(_ref(rq), C, dtype, a.ctypes.data, max(W * C, 1), ctypes.byref(cv), dst.ctypes.data, max(dW if planar else dW * C, 1),
+                                       max(dW * dH, 1), ctypes.byref(out_lay))
+    if rc != L.OK:
+        return rc, last_error(), None, None, None
+    return rc, "", dst, (out_lay.dst_iso_x, out_lay.dst_iso_y), out_lay
+
+
 def resample_multi_device(request, shards, src_stride, src_image_stride, dst_stride, dst_image_stride):
     """aai_resample_batch_multi_device_f32: `shards` is a list of (device, count, src_ptr, dst_ptr, stream) -- one batch of
     independent images spread over several GPUs of this process, no collective."""

@@ -29,6 +29,7 @@
 #include "../../include/aai_half_interleaved.h"
 #include "../../include/aai_adjoint_half.h"
 #include "../../include/aai_int.h"
+#include "../../include/ext/aai_convert.h"
 
 using namespace aai::engine;
 
@@ -701,6 +702,105 @@ int aai_resample_int_host(const aai_request *req, int32_t channels, int32_t dtyp
     return narrow_round_trip(*req, g, channels, aai::src_elem_size(dtype), src, src_stride, dst, dst_stride, layout, [&](const void *dSrc, void *dDst, hipStream_t stream) {
         return enqueue_int(*req, g, 1, channels, dtype, dSrc, (int64_t)g.W * channels, 0, dDst, (int64_t)g.dW * channels, 0, stream);
     });
+}
+
+// ---- include/ext/aai_convert.h: the checks of aai_resample_interleaved_device / _host in their order, the element type where the integer
+// entries check theirs, then the conversion's own.  The strides stand where the entry each is modelled on reports them: the device
+// entry's behind the device check (as enqueue() reports that entry's), the host entry's in front of the conversion's checks.
+static bool convert_planar(const aai_convert *cv) { return cv && cv->out_layout == AAI_LAYOUT_PLANAR; }
+
+static int check_convert(const aai_convert *cv, int channels)
+{
+    if (!cv) return fail(AAI_ERR_BAD_ARGUMENT, "Null conversion.");
+    if (cv->out_type != AAI_DTYPE_F32 && cv->out_type != AAI_HALF_F16 && cv->out_type != AAI_HALF_BF16) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown output element type.");
+    if (cv->out_layout != AAI_LAYOUT_INTERLEAVED && cv->out_layout != AAI_LAYOUT_PLANAR) return fail(AAI_ERR_BAD_ARGUMENT, "Unknown output layout.");
+    for (int c = 0; c < channels; ++c)
+        if (!std::isfinite(cv->scale[c]) || !std::isfinite(cv->offset[c])) return fail(AAI_ERR_NONFINITE, "Conversion scale and offset must be finite.");
+    return AAI_OK;
+}
+
+// check_strides with a planar destination's rows of dst_width elements
+static int check_convert_strides(const aai::Geometry &g, int channels, bool planar, int64_t srcStride, int64_t dstStride)
+{
+    if (!planar) return check_strides(g, channels, srcStride, dstStride);
+    if (srcStride < (int64_t)g.W * channels) return fail(AAI_ERR_BAD_ARGUMENT, "Source stride smaller than the image width.");
+    if (dstStride < (int64_t)g.dW) return fail(AAI_ERR_BAD_ARGUMENT, "Destination stride smaller than the output width.");
+    return AAI_OK;
+}
+
+static int check_convert_plane(const aai::Geometry &g, bool planar, int64_t dstStride, int64_t planeStride)
+{
+    if (planar && g.dW > 0 && g.dH > 0 && planeStride < (int64_t)(g.dH - 1) * dstStride + g.dW) return fail(AAI_ERR_BAD_ARGUMENT, "Destination plane stride smaller than one plane.");
+    return AAI_OK;
+}
+
+static aai::ConvertParams convert_params(const aai_convert &cv, int64_t planeStride)
+{
+    aai::ConvertParams p{};
+    p.outType = cv.out_type == AAI_DTYPE_F32 ? aai::CONVERT_F32 : (cv.out_type == AAI_HALF_F16 ? aai::CONVERT_F16 : aai::CONVERT_BF16);
+    p.planar = cv.out_layout == AAI_LAYOUT_PLANAR ? 1 : 0;
+    p.planeStride = planeStride;
+    for (int i = 0; i < 4; ++i) { p.scale[i] = cv.scale[i]; p.offset[i] = cv.offset[i]; }
+    return p;
+}
+
+int aai_resample_convert_device(const aai_request *req, int32_t batch, int32_t channels, int32_t src_dtype, const void *d_src, int64_t src_stride,
+                                int64_t src_image_stride, const aai_convert *cv, void *d_dst, int64_t dst_stride, int64_t dst_plane_stride,
+                                int64_t dst_image_stride, void *stream)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(check_batch(batch));
+    AAI_TRY(check_int_dtype(src_dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_row_length(g, channels));
+    if (batch > 0 && g.dW > 0 && g.dH > 0) AAI_TRY(check_pointers(d_src, d_dst));
+    AAI_TRY(check_convert(cv, channels));
+    const bool planar = convert_planar(cv);
+    return device_tail(batch == 0, [&] {
+        AAI_TRY(check_convert_strides(g, channels, planar, src_stride, dst_stride));
+        return check_convert_plane(g, planar, dst_stride, dst_plane_stride);
+    }, [&] {
+        return enqueue_convert(*req, g, batch, channels, src_dtype, d_src, src_stride, src_image_stride, convert_params(*cv, dst_plane_stride), d_dst, dst_stride,
+                               dst_image_stride, (hipStream_t)stream);
+    });
+}
+
+// (a host entry: one image up, one enqueue on the null stream, the wait, the image down -- a planar one plane by plane -- on dense device twins)
+int aai_resample_convert_host(const aai_request *req, int32_t channels, int32_t src_dtype, const void *src, int64_t src_stride, const aai_convert *cv, void *dst,
+                              int64_t dst_stride, int64_t dst_plane_stride, aai_layout *layout)
+{
+    aai::Geometry g;
+    AAI_TRY(check_request(req));
+    AAI_TRY(check_channels(channels));
+    AAI_TRY(check_int_dtype(src_dtype));
+    AAI_TRY(request_geometry(*req, g));
+    AAI_TRY(check_pointers(src, dst));
+    AAI_TRY(check_row_length(g, channels));
+    const bool planar = convert_planar(cv);
+    AAI_TRY(check_convert_strides(g, channels, planar, src_stride, dst_stride));
+    AAI_TRY(check_convert(cv, channels));
+    AAI_TRY(check_convert_plane(g, planar, dst_stride, dst_plane_stride));
+    AAI_TRY(require_device());
+    const size_t osz = cv->out_type == AAI_DTYPE_F32 ? sizeof(float) : sizeof(uint16_t);
+    const HostImage in = src_image(g, channels, src, src_stride, aai::src_elem_size(src_dtype));
+    // the device twin: dH rows of dW x channels elements, or `channels` planes of dH rows of dW elements
+    const int64_t row = planar ? (int64_t)g.dW : (int64_t)g.dW * channels;
+    const int planes = planar ? channels : 1;
+    const size_t planeBytes = osz * (size_t)row * (size_t)g.dH;
+    if (!planeBytes) return finish(*req, g, layout);
+    DeviceBuffer dIn, dOut;
+    hipStream_t stream = nullptr;
+    AAI_HIP(dIn.alloc(in.bytes()));
+    AAI_HIP(dOut.alloc(planeBytes * (size_t)planes));
+    AAI_HIP(hipMemcpy2D(dIn.p, in.esz * in.row, in.p, in.esz * in.stride, in.esz * in.row, in.rows, hipMemcpyHostToDevice));
+    AAI_TRY(enqueue_convert(*req, g, 1, channels, src_dtype, dIn.p, in.row, 0, convert_params(*cv, row * g.dH), dOut.p, row, 0, stream));
+    AAI_HIP(hipStreamSynchronize(stream));
+    for (int c = 0; c < planes; ++c)
+        AAI_HIP(hipMemcpy2D(static_cast<char *>(dst) + osz * (size_t)c * (size_t)dst_plane_stride, osz * dst_stride, dOut.as<char>() + planeBytes * (size_t)c, osz * row,
+                            osz * row, g.dH, hipMemcpyDeviceToHost));
+    return finish(*req, g, layout);
 }
 
 int aai_adjoint_prepare(const aai_request *req) { return adjoint_prepare(ADJOINT_PLANNED, req); }

@@ -946,9 +946,10 @@ struct NarrowSide {
 // and one conversion of out32 into `out`.  The scratch is stream-ordered from `device`'s pool: all of a chunk's widened inputs, each
 // rounded up to 256 bytes, then all its outputs.  aai_last_kernel(): what inner() left there, `suffix` appended.  A failed inner()
 // keeps its error text, whatever the free says; a failed launch is reported under its kernel's name.
-template <typename Inner>
-static int through_fp32_scratch(int type, bool widen, const NarrowSide &in, const NarrowSide &out, int batch, int device, const char *suffix,
-                                hipStream_t stream, Inner inner)
+// `store(nb, out32, b0) -> hipError_t` is that conversion for the nb images from image b0 on, reported as `storeName` when it fails.
+template <typename Inner, typename Store>
+static int through_fp32_scratch_into(int type, bool widen, const NarrowSide &in, const NarrowSide &out, int batch, int device, const char *suffix,
+                                     hipStream_t stream, const char *storeName, Inner inner, Store store)
 {
     const size_t inBytes = widen ? (in.count() * sizeof(float) + 255) & ~(size_t)255 : 0, outBytes = (out.count() * sizeof(float) + 255) & ~(size_t)255;
     const int chunk = chunk_images(batch, inBytes + outBytes);
@@ -958,7 +959,6 @@ static int through_fp32_scratch(int type, bool widen, const NarrowSide &in, cons
     char *scratch = nullptr;
     AAI_HIP(hipMallocFromPoolAsync((void **)&scratch, (inBytes + outBytes) * (size_t)chunk, pool, stream));
     float *in32 = reinterpret_cast<float *>(scratch), *out32 = reinterpret_cast<float *>(scratch + inBytes * (size_t)chunk);
-    const char *const storeName = aai::narrow_is_half(type) ? "aai_half_narrow_kernel" : "aai_int_quantize_kernel";
     const char *what = storeName;
     hipError_t e = hipSuccess;
     int rl = AAI_OK;
@@ -972,7 +972,7 @@ static int through_fp32_scratch(int type, bool widen, const NarrowSide &in, cons
         rl = inner(nb, widen ? (const void *)in32 : (const void *)in.image(type, b0), out32);
         if (rl != AAI_OK) break;
         what = storeName;
-        e = aai::launch_narrow_store(type, out32, const_cast<char *>(out.image(type, b0)), out.view, (int)out.row, out.rows, nb, stream);
+        e = store(nb, out32, b0);
     }
     const std::string lastError = g_lastError;      // (of a failed inner(): hipFreeAsync below must not replace it)
     const hipError_t ef = hipFreeAsync(scratch, stream);
@@ -981,6 +981,17 @@ static int through_fp32_scratch(int type, bool widen, const NarrowSide &in, cons
     if (e != hipSuccess) return hip_fail(e, what);
     if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     return AAI_OK;
+}
+
+// ... with the element type's own conversion into `out`: half_narrow or int_quantize
+template <typename Inner>
+static int through_fp32_scratch(int type, bool widen, const NarrowSide &in, const NarrowSide &out, int batch, int device, const char *suffix,
+                                hipStream_t stream, Inner inner)
+{
+    return through_fp32_scratch_into(type, widen, in, out, batch, device, suffix, stream, aai::narrow_is_half(type) ? "aai_half_narrow_kernel" : "aai_int_quantize_kernel",
+                                     inner, [&](int nb, const float *out32, int b0) {
+                                         return aai::launch_narrow_store(type, out32, const_cast<char *>(out.image(type, b0)), out.view, (int)out.row, out.rows, nb, stream);
+                                     });
 }
 
 // ---- the narrow-element paths (include/aai_half.h, include/aai_half_interleaved.h, include/aai_int.h; aai_axis_narrow.hip)
@@ -1086,6 +1097,48 @@ int enqueue_int(const aai_request &rq, const Geometry &g, int batch, int channel
 {
     const int type = srcType == aai::SRC_U8 ? aai::NARROW_U8 : aai::NARROW_U16;
     return enqueue_narrow(rq, g, batch, channels, type, dSrc, srcStride, srcImageStride, dDst, dstStride, dstImageStride, stream);
+}
+
+// ---- resample and convert (include/ext/aai_convert.h; aai_axis_convert.hip): routes in aai_engine.hpp
+int enqueue_convert(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
+                    const aai::ConvertParams &cv, void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream)
+{
+    if (g.dW == 0 || g.dH == 0 || batch == 0) return AAI_OK;
+    const int type = srcType == aai::SRC_U8 ? aai::NARROW_U8 : aai::NARROW_U16;
+    const int64_t rowDst = (int64_t)g.dW * channels;
+    const size_t nDst = (size_t)rowDst * (size_t)g.dH;
+    // the forward's plan under (request, channels), as enqueue_narrow acquires it for an integer image
+    PlanRef p;
+    const int rc = acquire_plan(rq, g, -1, -1, channels, rot_form(rq, g, channels, srcType, srcStride), &p, /*onCallerStream*/ true, stream);
+    if (rc != AAI_OK) return rc;
+    const int64_t elem = (int64_t)aai::narrow_elem_size(type), outElem = (int64_t)aai::convert_out_size(cv.outType);
+    const char *src = static_cast<const char *>(dSrc);
+    char *dst = static_cast<char *>(dDst);
+    const aai::ImageView sv{srcStride, srcImageStride}, dv{dstStride, dstImageStride};
+    hipError_t e = hipSuccess;
+    if (p->kernel == AAI_KERNEL_AXIS && !p->dense && p->flaggedPixels == 0 && (rq.mode == AAI_MODE_AREA || rq.mode == AAI_MODE_FAST)) {
+        // (the tables and the launch block are read-only here: no side stream, no event, hence no lock)
+        const aai::AxisLaunch a = make_axis_launch(*p, channels, dstStride);
+        if (aai::axis_convert_can_serve(a, type, cv.outType, cv.planar)) {
+            const char *name = "";
+            for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridZ)
+                e = aai::launch_axis_convert(a, type, cv, src + (int64_t)b0 * srcImageStride * elem, sv, dst + (int64_t)b0 * dstImageStride * outElem, dv,
+                                             std::min(batch - b0, kMaxGridZ), stream, &name);
+            g_lastKernel = name;
+            if (e != hipSuccess) return hip_fail(e, name);
+            return AAI_OK;
+        }
+    }
+    // forwarding: the fp32 entry's launches into dense fp32 scratch (enqueue() reads u8 / u16 itself), one conversion -- the bits of
+    // round(fma(fp32 entry(src), scale, offset))
+    const NarrowSide in{dSrc, sv, (int64_t)g.W * channels, g.H}, out{dDst, dv, rowDst, g.dH};
+    return through_fp32_scratch_into(type, false, in, out, batch, p->device, "+converted", stream, "aai_convert_store_kernel",
+                                     [&](int nb, const void *in32, float *out32) {
+                                         return enqueue(rq, g, nb, in32, srcType, srcStride, srcImageStride, out32, rowDst, (int64_t)nDst, stream, -1, -1, channels);
+                                     },
+                                     [&](int nb, const float *out32, int b0) {
+                                         return aai::launch_convert_store(cv, channels, out32, dst + (int64_t)b0 * dstImageStride * outElem, dv, g.dW, g.dH, nb, stream);
+                                     });
 }
 
 int require_device()

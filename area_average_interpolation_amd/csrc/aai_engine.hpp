@@ -239,6 +239,17 @@ int enqueue_half(const aai_request &rq, const Geometry &g, int batch, int channe
 int enqueue_int(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
                 void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
 
+// Resample and convert (include/ext/aai_convert.h; the caller has checked the arguments, strides included): u8 / u16 images (srcType =
+// SRC_U8 / SRC_U16) of `channels` interleaved channels in, round(fma(s, scale[c], offset[c])) out in cv's type and layout (dstStride,
+// cv.planeStride and dstImageStride in elements of the output type), every mode.  enqueue_narrow's plan and two routes:
+//   DIRECT      kernel AXIS, not dense, no listed pixel, area or fast mode, aai::axis_convert_can_serve: aai_axis_convert_kernel reads the
+//               integer image and writes the converted image, no scratch, the batch split at kMaxGridZ.  aai_last_kernel():
+//               "aai_axis_convert_kernel<u8|u16,f32|f16|bf16>".
+//   FORWARDING  everything else: enqueue() into dense fp32 output scratch (through_fp32_scratch_into's pool and chunks),
+//               aai_convert_store_kernel into the caller's buffer.  aai_last_kernel(): "<fp32 name>+converted".
+int enqueue_convert(const aai_request &rq, const Geometry &g, int batch, int channels, int srcType, const void *dSrc, int64_t srcStride, int64_t srcImageStride,
+                    const aai::ConvertParams &cv, void *dDst, int64_t dstStride, int64_t dstImageStride, hipStream_t stream);
+
 // The half-precision adjoint (include/aai_adjoint_half.h; the caller has checked the arguments): gsrc = narrow(W^T widen(gdst)) for `batch`
 // fp16 / bf16 images (halfType = AAI_HALF_F16 / AAI_HALF_BF16) of raw 16-bit elements with `channels` = 1..4 interleaved channels, area /
 // fast modes, strides in elements.  On both routes the bits of narrow(enqueue_adjoint(ADJOINT_SEPARABLE, widen(gdst))).  The plan is

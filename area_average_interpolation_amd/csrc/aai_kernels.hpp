@@ -196,6 +196,30 @@ hipError_t launch_narrow_widen(int type, const void *src, ImageView sv, float *d
 // of the type: half_narrow or int_quantize.  `batch` <= 65535.
 hipError_t launch_narrow_store(int type, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream);
 
+// ---- resample and convert (aai_axis_convert.hip; include/ext/aai_convert.h): u8 / u16 in, scaled fp32 / fp16 / bf16 out ----
+// out = round(fma(s, scale[c], offset[c])) in `outType` (CONVERT_F32: not rounded), interleaved (element (x, y, c) at y * rowStride +
+// x * channels + c of dv) or planar (c * planeStride + y * rowStride + x).  Strides in elements of the output type.
+enum ConvertOut { CONVERT_F32 = 0, CONVERT_F16 = 1, CONVERT_BF16 = 2 };      // AAI_DTYPE_F32 / AAI_HALF_F16 / AAI_HALF_BF16
+struct ConvertParams {
+    int outType;      // ConvertOut
+    int planar;
+    int64_t planeStride;
+    float scale[4], offset[4];
+};
+constexpr bool convert_out_known(int outType) { return outType >= CONVERT_F32 && outType <= CONVERT_BF16; }
+constexpr size_t convert_out_size(int outType) { return outType == CONVERT_F32 ? 4 : 2; }
+// The direct kernel over K1's tables: whether it serves a launch block (the static facts of axis_narrow_can_serve for an integer
+// source type `srcType`: NARROW_U8 / NARROW_U16, and the measured rule of profiles/convert_time.txt) ...
+bool axis_convert_can_serve(const AxisLaunch &a, int srcType, int outType, int planar);
+// ... and its launch (hipErrorInvalidValue where it does not).  a: make_axis_launch's block for `channels` and the dst row stride (its
+// flips and tables are read; the dst mapping is the convert kernel's own).  No scratch.  `batch` <= 65535.  *kernelName:
+// "aai_axis_convert_kernel<u8|u16,f32|f16|bf16>".
+hipError_t launch_axis_convert(const AxisLaunch &a, int srcType, const ConvertParams &cv, const void *src, ImageView sv, void *dst, ImageView dv, int batch,
+                               hipStream_t stream, const char **kernelName);
+// dense fp32 interleaved images (H rows of W pixels x channels elements, image b at b * W * channels * H) -> pitched converted images:
+// the forwarding route's last stage.  `batch` <= 65535.
+hipError_t launch_convert_store(const ConvertParams &cv, int channels, const float *src, void *dst, ImageView dv, int W, int H, int batch, hipStream_t stream);
+
 // ---- the half-precision transposed separable kernel (aai_axis_adjoint_narrow.hip; body in aai_axis_adjoint_half_math.hpp) ----
 // launch_axis_adjoint_multi's launch block (a.srcW / a.srcH in pixels, the mapping of PIXELS onto elements of gdst, the single-channel
 // plan's tables) for `channels` = 1..4 on fp16 / bf16 images (`type`: NARROW_F16 / NARROW_BF16) of raw 16-bit elements: the bits of

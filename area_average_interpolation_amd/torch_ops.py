@@ -305,6 +305,67 @@ def _resample_int(x, src_resolution, dst_resolution, src_isocenter, rotation_ang
     return y, iso
 
 
+_CONVERT_DTYPES = {torch.float32: L.DTYPE_F32, torch.float16: L.HALF_F16, torch.bfloat16: L.HALF_BF16}
+
+
+def _resample_convert(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, out_dtype, scale, offset, out_memory_format):
+    """resample(..., integer=True, out_dtype=...): uint8 / uint16 tensors in, a scaled float32 / float16 / bfloat16 tensor out, written by
+    the library in its final memory format (include/ext/aai_convert.h); no autograd"""
+    if x.dtype not in _INT_DTYPES:
+        raise TypeError("resample(integer=True) takes a uint8 or uint16 tensor, got %s" % x.dtype)
+    if out_dtype not in _CONVERT_DTYPES:
+        raise ValueError("resample(out_dtype=...) takes torch.float32, torch.float16 or torch.bfloat16, got %r" % (out_dtype,))
+    if out_memory_format not in (torch.contiguous_format, torch.channels_last):
+        raise ValueError("resample(out_memory_format=...) takes torch.contiguous_format or torch.channels_last, got %r" % (out_memory_format,))
+    if x.dim() not in (2, 3, 4):
+        raise ValueError("resample() takes a tensor of shape (H, W), (B, H, W) or (B, C, H, W)")
+    nhwc_out = out_memory_format == torch.channels_last
+    if nhwc_out and x.dim() != 4:
+        raise ValueError("resample(out_memory_format=torch.channels_last) takes a tensor of shape (B, C, H, W)")
+    if x.dim() == 4 and x.shape[1] > 4:
+        raise ValueError("resample(integer=True) takes at most 4 channels, got %d" % x.shape[1])
+    C = x.shape[1] if x.dim() == 4 else 1
+    convert = api.make_convert(max(C, 1), _CONVERT_DTYPES[out_dtype], False, scale, offset)      # (checks the lengths of scale and offset)
+    if not x.is_cuda:
+        raise ValueError("resample() takes a tensor on a GPU (the library has no CPU path)")
+    H, W = x.shape[-2], x.shape[-1]
+    rq, lay = _query(W, H, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy)
+    iso = (lay.dst_iso_x, lay.dst_iso_y)
+    dH, dW = lay.dst_height, lay.dst_width
+    lead = tuple(x.shape[:-2])
+    x = x.detach()
+    y = torch.empty(lead + (dH, dW), dtype=out_dtype, device=x.device, **({"memory_format": torch.channels_last} if nhwc_out else {}))
+    if 0 in lead or dH == 0 or dW == 0:
+        return y, iso
+    src_dtype, stream = _INT_DTYPES[x.dtype], None
+    # (B, C, H, W) with C > 1: dense in channels_last the NHWC storage is the library's interleaved layout and is read in place; a
+    # contiguous one that goes to a contiguous y runs plane by plane, also in place; a contiguous one that goes to channels_last is
+    # brought into channels_last first (a copy of the integer tensor: the one case that copies)
+    interleaved = C > 1 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+    if C > 1 and not interleaved and nhwc_out:
+        x = x.contiguous(memory_format=torch.channels_last)
+        interleaved = True
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        if interleaved:
+            B = x.shape[0]
+            _ensure_prepared(rq, C)
+            convert.out_layout = L.LAYOUT_INTERLEAVED if nhwc_out else L.LAYOUT_PLANAR
+            api.resample_convert_device(rq, C, x.data_ptr(), W * C, y.data_ptr(), dW * C if nhwc_out else dW, src_dtype, convert, stream=stream, batch=B,
+                                        src_image_stride=H * W * C, dst_image_stride=dH * dW * C, dst_plane_stride=dH * dW)
+        else:
+            # single-channel images: every image of a (H, W) / (B, H, W) tensor at once, or plane c of every image of a contiguous
+            # (B, C, H, W) tensor with its channel's scale and offset
+            x = x.contiguous()
+            _ensure_prepared(rq, 1)
+            images = x.numel() // max(H * W * C, 1)
+            for c in range(C):
+                one = api.make_convert(1, _CONVERT_DTYPES[out_dtype], False, convert.scale[c], convert.offset[c])
+                api.resample_convert_device(rq, 1, x.data_ptr() + c * H * W * x.element_size(), W, y.data_ptr() + c * dH * dW * y.element_size(), dW, src_dtype, one,
+                                            stream=stream, batch=images, src_image_stride=H * W * C, dst_image_stride=dH * dW * C)
+    return y, iso
+
+
 class _ResampleInterleaved(torch.autograd.Function):
     """(B, C, H, W) dense in torch.channels_last, 2 <= C <= 4: the NHWC storage is the library's interleaved layout, nothing is copied"""
 
@@ -463,7 +524,8 @@ def _nchw_route(interleaved, lay, mode, planned, sampler_backward):
 
 
 def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode=L.MODE_AREA, policy=L.POLICY_REFERENCE,
-             *positional, sampler_backward=False, f64=False, half=False, integer=False, half_backward=False, planned_backward=False):
+             *positional, sampler_backward=False, f64=False, half=False, integer=False, half_backward=False,
+             out_dtype=None, scale=None, offset=None, out_memory_format=torch.contiguous_format, planned_backward=False):
     """Resample a CUDA/HIP fp32 tensor of shape (H, W), (B, H, W) or (B, C, H, W); returns ``(y, dst_isocenter)`` with y of shape
     (dH, dW), (B, dH, dW) or (B, C, dH, dW).  Differentiable ONCE with respect to x in the area and fast modes (a double backward raises; the
     bilinear / bicubic comparison paths are differentiable only with sampler_backward=True, below: without it an x that requires grad
@@ -593,6 +655,18 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
     (integers carry no gradient): y never requires grad.  integer=True together with half, f64, planned_backward or sampler_backward
     raises ValueError.
 
+    out_dtype: None (the default) -- nothing changes.  torch.float32, torch.float16 or torch.bfloat16, with integer=True (without it:
+    ValueError) -- resample and convert (include/ext/aai_convert.h): x is a uint8 / uint16 tensor exactly as integer=True takes it, y is a
+    tensor of out_dtype holding round(fma(s, scale[c], offset[c])): the fp32 sums s of the integer values, ONE fused multiply-add in fp32,
+    ONE rounding to out_dtype (to nearest, ties to even; beyond the largest finite float16: +-Inf).  scale / offset: a scalar or one value
+    per channel (defaults 1 and 0; finite).  out_memory_format: torch.contiguous_format (y is planar, NCHW) or torch.channels_last (y has
+    NHWC storage; (B, C, H, W) tensors only); the library writes y in that format, nothing is permuted or cast afterwards.  A (B, C, H, W)
+    x dense in channels_last is read in place; a contiguous one going to a contiguous y runs plane by plane in place; a contiguous one
+    going to channels_last is copied into channels_last first.  Rotations by 0 / 180 degrees in the area / fast modes run one kernel from
+    the integer tensor to y, every other request runs the fp32 forward into scratch and converts.  y never requires grad.  out_dtype
+    together with half, f64, planned_backward, sampler_backward or half_backward raises ValueError; scale, offset or a channels_last
+    out_memory_format without out_dtype raise ValueError.
+
     B == 0 or C == 0 returns an empty tensor of the output's shape without a launch."""
     # planned_backward keeps its place as the eighth positional argument (*positional holds at most that one); sampler_backward is
     # keyword-only
@@ -602,6 +676,14 @@ def resample(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, m
         planned_backward = positional[0]
     if not isinstance(x, torch.Tensor):
         raise TypeError("resample() takes a torch.Tensor")
+    if out_dtype is not None:
+        if not integer:
+            raise ValueError("resample(out_dtype=...) converts integer tensors: it needs integer=True")
+        if half or f64 or planned_backward is not False or sampler_backward or half_backward:
+            raise ValueError("resample(integer=True, out_dtype=...) has no gradient: it takes none of half, f64, planned_backward, sampler_backward, half_backward")
+        return _resample_convert(x, src_resolution, dst_resolution, src_isocenter, rotation_angle, mode, policy, out_dtype, scale, offset, out_memory_format)
+    if scale is not None or offset is not None or out_memory_format != torch.contiguous_format:
+        raise ValueError("resample(): scale, offset and out_memory_format belong to out_dtype (with integer=True)")
     if isinstance(half, str) and half != "channels_last":
         raise ValueError('half must be False, True or "channels_last", got %r' % (half,))
     if half_backward:

@@ -1346,7 +1346,8 @@ def test_sources_larger_than_4_gib(gpu, po):
     (QuadMap::rebaseWaves), in every quadrant.  Sampled row bands against the CPU oracle's rows.
     (Dense images, plain fp32, three ratios.  Every family, source type, interleaved images, the 8 MiB pitch, the bounds of
     cell_can_serve / quad_can_address, destinations and batches of that size, and the adjoints: tests/test_wide_pitch_gpu.py, on small
-    images in wide-pitch views, every pixel against the oracle.)"""
+    images in wide-pitch views, every pixel against the oracle; the half, integer, convert and half-adjoint entries:
+    tests/test_wide_pitch_typed_gpu.py.)"""
     import torch
     st = torch.cuda.current_stream().cuda_stream
     for (W, H, cases) in ((33000, 33000, ((4.0, 1.0, 0.0, 1, po.MODE_EXACT), (3.0, 1.0, 17.5, 1, po.MODE_EXACT), (3.0, 1.0, 17.5, 2, po.MODE_FAST),

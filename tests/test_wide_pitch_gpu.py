@@ -297,6 +297,7 @@ ADJOINTS = [
     ("rotated-plain-rgb", "adjoint_interleaved_device", dict(planned="any"), "f32", 1, 3.0, 287.5, 40, 3),
     ("sample-bilinear", "adjoint_sample_device", {}, "f32", 3, 2.0, 17.5, 100, 1),
     ("sample-bicubic", "adjoint_sample_device", {}, "f32", 4, 2.0, 107.5, 100, 1),
+    ("sample-bilinear-rgb", "adjoint_sample_interleaved_device", {}, "f32", 3, 2.0, 17.5, 40, 3),
     ("f64-adjoint", "adjoint_device_f64", {}, "f64", 1, 3.0, 17.5, 100, 1),
     ("f64-adjoint-fast", "adjoint_device_f64", {}, "f64", 2, 3.0, 107.5, 100, 1),
     ("f64-forward", "resample_device_f64", {}, "f64", 1, 3.0, 17.5, 100, 1),
